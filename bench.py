@@ -8,7 +8,13 @@ that were timed (untimed re-run).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c4|ref] [--camera still|orbit]
                     [--row-stripe S] [--one-process] [--transport rccl|copy|direct] [--devices 0,1,..] [--verify]
-                    [--rccl-rehearsal] [--no-cpu-baseline]
+                    [--rccl-rehearsal] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps, counts their rays (above COUNT_STEPS_MAX steps: in that many of
+the timed frames, evenly spaced; counted_steps), writes the last timed frame if --dump-outputs is given, and prints
+the line. --full counts every timed frame at any K and adds everything else the benchmark measures: the kernel time of the steps (HIP
+events), the roofline priced from it, the executed-work figures of configs with samples > 1 and the CPU baseline
+(--no-cpu-baseline leaves that one out).
 
 Prints one JSON line on rank 0 (its "launch" field names how the ranks were started). Every mode drives the
 product's C ABI (include/wcpt.h wcpt_group_*) on the system HIP runtime (/opt/rocm), as the Jai host would; torch is
@@ -388,7 +394,15 @@ def parse_args(argv=None):
                     help="still: progressive frames of a still camera (renderedFramesCount = 0, 1, ...); orbit: the "
                          "camera moves every frame as in an editor drag (strafe + yaw, renderedFramesCount = 0 each "
                          "frame, editor.jai:149-150), so the primary-ray records are rebuilt for every frame")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the kernel time of the timed steps (HIP events; at N > 1 an "
+                         "untimed re-render), the roofline, the executed-work figures (samples > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame the last of them presented (what a caller of the "
+                         "render path reads back) to DIR/frame.npy as float32, NaN and infinite channels as 0.0 and "
+                         "named per pixel in DIR/frame_nonfinite.npy; a frame above DUMP_MAX_BYTES is written as a "
+                         "fixed, seeded sample of its pixels, with their indices in DIR/frame_pixels.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--pmc-json", default=None,
                     help="PMC HBM-traffic summary for roofline.traffic (default profiles/pmc_traffic_<config>.json, "
@@ -930,6 +944,59 @@ def verify_frame(args, topo, scene, W, H, spp, bounces, frames: FrameSource, nfr
     return ok
 
 
+COUNT_STEPS_MAX = 1024  # a plain run counts the work of at most this many of its timed frames
+
+
+def counted_steps(steps: int, full: bool) -> list:
+    """The timed steps whose frames the instrumented kernel renders again to count their segments. An instrumented c2
+    frame takes ~2.8 ms against 0.34 ms for the render, so a plain run of many steps counts COUNT_STEPS_MAX of them,
+    the middle one of as many equal stretches of the run (a function of `steps` alone: the same frames in every run
+    and on every rank), and scales the sums to all steps; segments per frame of one workload vary by parts in 10^4
+    from frame to frame, their mean over 1024 frames by parts in 10^5. Up to COUNT_STEPS_MAX steps, and always with
+    --full, every timed frame is counted."""
+    if full or steps <= COUNT_STEPS_MAX:
+        return list(range(steps))
+    return [(2 * i + 1) * steps // (2 * COUNT_STEPS_MAX) for i in range(COUNT_STEPS_MAX)]
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much
+DUMP_SEED = 0x57435054             # of the pixel sample of a larger frame: the same pixels in every run
+
+
+def _nonfinite_codes(px: np.ndarray) -> np.ndarray:
+    """One float32 per pixel of px [..., C] (C <= 4): 0 where every channel is finite, else the sum over channels c of
+    code_c * 4**c with code 1 = NaN, 2 = +inf, 3 = -inf (at most 255, exact in float32)."""
+    code = np.isnan(px) * 1 + np.isposinf(px) * 2 + np.isneginf(px) * 3
+    return (code * (4 ** np.arange(px.shape[-1]))).sum(axis=-1).astype(np.float32)
+
+
+def dump_outputs(path: str, frame: np.ndarray) -> dict:
+    """--dump-outputs: the presented frame ([H, W, 4]; the display format's bytes as float32 too) as path/frame.npy.
+    The reference's algorithm, which the kernels follow bit for bit, leaves NaN in a pixel now and then (c2: pixels
+    (421, 511) and (46, 1118) at frames 624 and 625, in the CPU oracle as on the GPU), and progressive accumulation
+    keeps it there; so that every value written is finite, such channels are written as
+    0.0 in frame.npy and named in path/frame_nonfinite.npy (one value per pixel, _nonfinite_codes; all 0.0 for a
+    finite frame), and the two files together hold what the caller received. A frame that would take more than
+    DUMP_MAX_BYTES so (c4) is written as [n, 4] pixels drawn without replacement by a fixed seed, in raster order,
+    beside their flat pixel indices (path/frame_pixels.npy, float64). Returns what it wrote."""
+    os.makedirs(path, exist_ok=True)
+    img = np.ascontiguousarray(frame, dtype=np.float32)
+    ch = img.shape[-1]
+    info = {}
+    if img.nbytes // ch * (ch + 1) + 4096 > DUMP_MAX_BYTES:
+        px = img.reshape(-1, ch)
+        n = (DUMP_MAX_BYTES - 4096) // (ch * 4 + 4 + 8)  # a pixel, its code and its index; room for the .npy headers
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(px.shape[0], size=n, replace=False))
+        np.save(os.path.join(path, "frame_pixels.npy"), idx.astype(np.float64))
+        info = {"frame_pixels": [int(n)], "sampled_from": list(img.shape)}
+        img = px[idx]
+    codes = _nonfinite_codes(img)
+    np.save(os.path.join(path, "frame.npy"), np.where(np.isfinite(img), img, np.float32(0.0)))
+    np.save(os.path.join(path, "frame_nonfinite.npy"), codes)
+    return {"frame": list(img.shape), "frame_nonfinite": list(codes.shape),
+            "nonfinite_pixels": int(np.count_nonzero(codes)), **info}
+
+
 def _gpu_identity(device: int) -> str:
     try:
         return wcpt.device_pci_bus_id(device)
@@ -1028,7 +1095,8 @@ def main(argv=None):
     # (profiles/r05_events_ab.log). With more ranks the events are left out of the timed region (at 8 ranks a c2 block
     # renders in ~0.07 ms, and event records per render and rank are host work of that order): the same frames are
     # re-rendered afterwards, untimed, with a pair of events around every render and presenting off.
-    live_events = nranks == 1 and not args.events_after
+    # All of it belongs to --full: a plain run records no event and re-renders nothing.
+    live_events = args.full and nranks == 1 and not args.events_after
     if live_events:
         drv.profile_begin(region=True)
     t0 = time.perf_counter()
@@ -1037,21 +1105,27 @@ def main(argv=None):
     drv.sync()
     elapsed = time.perf_counter() - t0
     coll.barrier()
-    got = drv.frame() if args.verify else None
-    if not live_events:
-        drv.presenting(False)
-        drv.profile_begin()
-        for k in range(args.steps):
-            drv.render(frames(args.warmup + k))
-    prof = drv.profile_end()
+    got = drv.frame() if args.verify or args.dump_outputs else None
+    dumped = dump_outputs(args.dump_outputs, got) if args.dump_outputs and got is not None else None
+    prof = []
+    if args.full:
+        if not live_events:
+            drv.presenting(False)
+            drv.profile_begin()
+            for k in range(args.steps):
+                drv.render(frames(args.warmup + k))
+        prof = drv.profile_end()
     drv.sync()  # surfaces a traversal-stack overflow, if any
 
     # exact work of the timed frames (instrumented kernel, untimed), this process's ranks
     tot = {}
-    for k in range(args.steps):
+    counted = counted_steps(args.steps, args.full)
+    for k in counted:
         for n, v in drv.counters(frames.copy(args.warmup + k)).items():
             tot[n] = max(tot.get(n, 0), v) if n == "ref_stack_max" else tot.get(n, 0) + v
-    if spp > 1:
+    if len(counted) < args.steps:  # a plain run of many steps: the counted frames stand for all of them
+        tot = {n: v if n == "ref_stack_max" else int(round(v * args.steps / len(counted))) for n, v in tot.items()}
+    if spp > 1 and args.full:
         # primary segments (samples = 1, no bounce): the same rays every sample of a frame traces first; the render
         # traces them once per pixel and samples 1..spp-1 reuse that record (pt_wavefront.hip wf_shade, pt_device.h)
         sd0 = frames.copy(args.warmup)
@@ -1076,9 +1150,6 @@ def main(argv=None):
         for a in allr:
             for n, v in a["tot"].items():
                 T[n] = max(T.get(n, 0), v) if n == "ref_stack_max" else T.get(n, 0) + v
-        blocks = sorted((b for a in allr for b in a["per_rank"]), key=lambda b: b["rank"])
-        # the roofline's kernel time: the slowest rank's average render (with one rank, the render itself)
-        avg_kernel_s = max(b["block_ms"] for b in blocks) / 1e3
         ms_per_step = elapsed_max / args.steps * 1e3
         segs_all, prim_all = float(T["segments"]), float(T["pixels"] * spp)
         value = segs_all / elapsed_max / 1e6
@@ -1098,6 +1169,7 @@ def main(argv=None):
             "steps": args.steps,
             "warmup": args.warmup,
             "settle_ms": args.settle_ms,
+            "full": bool(args.full),
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "strong",
@@ -1126,20 +1198,31 @@ def main(argv=None):
             "build_id": args.build_id,
             "primary_mrays_per_s": round(prim_all / elapsed_max / 1e6, 3),
             "segments_per_frame": int(segs_all / args.steps),
-            "kernel_ms_avg": round(avg_kernel_s * 1e3, 4),
-            "kernel_launches_per_frame": round(sum(a["launches"] for a in allr) / max(1, len(blocks)) / args.steps, 2),
-            "kernel_timing": ("two HIP events on the render stream bracketing the timed renders: launch duration = "
-                              "their interval / renders (inter-launch gaps included)" if live_events
-                              else "HIP events around each render on each rank's render stream, in an untimed "
-                                   "re-render of the timed frames (N > 1: kept out of the timed steps); the slowest "
-                                   "rank's average"),
+            "segments_counted": ("in every timed frame" if len(counted) == args.steps else
+                                 f"in {len(counted)} of the {args.steps} timed frames, evenly spaced, and scaled to all "
+                                 f"of them (--full counts every frame)"),
             "ref_stack": {"overflow_segments": T["ref_stack_overflow_segments"], "max": T["ref_stack_max"],
                           "note": "segments of the timed frames that would write past the reference's uint "
                                   "nodeStack[32] (pathTracer.comp:151), and the deepest stack they reach"},
-            "roofline": roofline(args, T, avg_kernel_s, ms_per_step / 1e3, devices=distinct, ranks=nranks),
         }
+        if dumped is not None:
+            out["dumped"] = dumped
+        if args.full:
+            blocks = sorted((b for a in allr for b in a["per_rank"]), key=lambda b: b["rank"])
+            # the roofline's kernel time: the slowest rank's average render (with one rank, the render itself)
+            avg_kernel_s = max(b["block_ms"] for b in blocks) / 1e3
+            out["kernel_ms_avg"] = round(avg_kernel_s * 1e3, 4)
+            out["kernel_launches_per_frame"] = round(sum(a["launches"] for a in allr) / max(1, len(blocks))
+                                                     / args.steps, 2)
+            out["kernel_timing"] = ("two HIP events on the render stream bracketing the timed renders: launch "
+                                    "duration = their interval / renders (inter-launch gaps included)" if live_events
+                                    else "HIP events around each render on each rank's render stream, in an untimed "
+                                         "re-render of the timed frames (N > 1: kept out of the timed steps); the "
+                                         "slowest rank's average")
+            out["roofline"] = roofline(args, T, avg_kernel_s, ms_per_step / 1e3, devices=distinct, ranks=nranks)
+            if nranks > 1:
+                out["per_rank_block_ms"] = [b["block_ms"] for b in blocks]
         if nranks > 1:
-            out["per_rank_block_ms"] = [b["block_ms"] for b in blocks]
             if topo["mode"] == "group" and transport == "rccl" and distinct > 1:
                 out["unrehearsed"] = ("the one-process RCCL group (ncclCommInitAll, every rank issued from one thread) "
                                       "over several GPUs has never run on hardware before this line; the default "
@@ -1149,7 +1232,7 @@ def main(argv=None):
                 if args.rccl_rehearsal:
                     out["rehearsal"] += (" (RCCL with a NCCL_HOSTID per rank: ncclCommInitRank, ncclSend / ncclRecv "
                                          "over RCCL's socket transport instead of xGMI)")
-        if spp > 1:
+        if spp > 1 and args.full:
             # samples 1..spp-1 shade their primary segment from sample 0's Intersect record (same ray): the reference
             # executes those segments, this implementation does not (pathTracer.comp:309-310)
             executed = segs_all - float(T["reused_primary_segments"])
@@ -1160,7 +1243,7 @@ def main(argv=None):
                                  "sample 0's record")
         if verified is not None:
             out["verified"] = verified
-        if nranks == 1 and not args.no_cpu_baseline:
+        if args.full and nranks == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, W, H, spp, bounces, budget_s=args.cpu_seconds)
             out["speedup_vs_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
             if "per_gpu_share" in out["cpu_baseline"]:

@@ -267,3 +267,68 @@ def test_frame_overlap_flag():
     import wcpt
     hdr = open(os.path.join(ROOT, "include", "wcpt.h")).read()
     assert "#define WCPT_OPTION_FRAME_OVERLAP 15" in hdr and wcpt._lib.OPTION_FRAME_OVERLAP == 15
+
+
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the size limit is written whole as float32 (the display format's bytes too); a
+    larger one as a pixel sample that is the same in every run, in raster order, with the pixels' flat indices, and
+    the files together stay within the limit. Every value written is finite: a NaN or infinite channel is written as
+    0.0 and named in frame_nonfinite.npy, from which the frame the caller received can be put together again."""
+    a = bench.parse_args(["--dump-outputs", "d", "--full"])
+    assert a.dump_outputs == "d" and a.full and not bench.parse_args([]).full and bench.parse_args([]).dump_outputs is None
+    assert bench.DUMP_MAX_BYTES <= 64 * 1000 * 1000
+    assert 1920 * 1080 * (16 + 4) + 4096 <= bench.DUMP_MAX_BYTES          # a 1080p frame and its codes: whole
+    rng = np.random.default_rng(3)
+    img = rng.random((37, 53, 4), dtype=np.float32)
+    info = bench.dump_outputs(str(tmp_path / "a"), img)
+    assert info == {"frame": [37, 53, 4], "frame_nonfinite": [37, 53], "nonfinite_pixels": 0}
+    got, codes = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "frame_nonfinite.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    assert codes.dtype == np.float32 and codes.shape == (37, 53) and not codes.any()
+    u8 = rng.integers(0, 256, (5, 7, 4), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "b"), u8)
+    got = np.load(tmp_path / "b" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, u8.astype(np.float32))
+    # non-finite channels: 1 = NaN, 2 = +inf, 3 = -inf, times 4**channel, summed per pixel
+    bad = img.copy()
+    bad[0, 0, :3], bad[3, 5, 1], bad[36, 52, 3], bad[7, 7] = np.nan, np.inf, -np.inf, (np.nan, np.inf, -np.inf, 1.0)
+    info = bench.dump_outputs(str(tmp_path / "n"), bad)
+    got, codes = np.load(tmp_path / "n" / "frame.npy"), np.load(tmp_path / "n" / "frame_nonfinite.npy")
+    assert info["nonfinite_pixels"] == 4 and np.isfinite(got).all() and np.isfinite(codes).all()
+    assert (codes[0, 0], codes[3, 5], codes[36, 52], codes[7, 7]) == (1 + 4 + 16, 2 * 4, 3 * 64, 1 + 2 * 4 + 3 * 16)
+    assert np.count_nonzero(codes) == 4 and np.array_equal(got[np.isfinite(bad)], bad[np.isfinite(bad)])
+    assert not got[~np.isfinite(bad)].any()
+    digit = (codes.astype(np.int64)[..., None] // 4 ** np.arange(4)) % 4
+    back = np.where(digit == 1, np.nan, np.where(digit == 2, np.inf, np.where(digit == 3, -np.inf, got)))
+    assert np.array_equal(back.astype(np.float32).view(np.uint32) & 0x7F800000 == 0x7F800000, ~np.isfinite(bad))
+    assert np.array_equal(np.isnan(back), np.isnan(bad)) and np.array_equal(back[~np.isnan(bad)], bad[~np.isnan(bad)])
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16384)
+    info = bench.dump_outputs(str(tmp_path / "c"), bad)
+    px, idx = np.load(tmp_path / "c" / "frame.npy"), np.load(tmp_path / "c" / "frame_pixels.npy")
+    codes = np.load(tmp_path / "c" / "frame_nonfinite.npy")
+    n = px.shape[0]
+    assert info == {"frame": [n, 4], "frame_nonfinite": [n], "nonfinite_pixels": int(np.count_nonzero(codes)),
+                    "frame_pixels": [n], "sampled_from": [37, 53, 4]}
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and idx.shape == (n,) and 300 < n < 37 * 53
+    src = bad.reshape(-1, 4)[idx.astype(np.int64)]
+    assert np.all(np.diff(idx) > 0) and np.isfinite(px).all()
+    assert np.array_equal(px[np.isfinite(src)], src[np.isfinite(src)]) and not px[~np.isfinite(src)].any()
+    assert np.array_equal(codes != 0, ~np.isfinite(src).all(axis=1))
+    assert sum(os.path.getsize(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")) <= 16384
+    bench.dump_outputs(str(tmp_path / "e"), bad)
+    assert np.array_equal(np.load(tmp_path / "e" / "frame_pixels.npy"), idx)
+
+
+def test_counted_steps_of_a_plain_and_a_full_run():
+    """Up to COUNT_STEPS_MAX timed steps, and with --full at any length, the instrumented kernel counts every timed
+    frame; a longer plain run counts COUNT_STEPS_MAX of them: distinct, increasing, one from each equal stretch of the
+    run, and the same ones whenever it is asked."""
+    m = bench.COUNT_STEPS_MAX
+    assert bench.counted_steps(20, False) == list(range(20)) and bench.counted_steps(m, False) == list(range(m))
+    assert bench.counted_steps(5 * m + 3, True) == list(range(5 * m + 3))
+    for steps in (m + 1, 2 * m, 5 * m + 3, 100 * m + 17):
+        c = bench.counted_steps(steps, False)
+        assert len(c) == m and c == bench.counted_steps(steps, False)
+        assert c[0] >= 0 and c[-1] < steps and all(b > a for a, b in zip(c, c[1:]))
+        # step k is the one that holds the middle of stretch i, (i + 1/2) * steps / m
+        assert all(2 * k * m <= (2 * i + 1) * steps < 2 * (k + 1) * m for i, k in enumerate(c))

@@ -58,6 +58,9 @@ def _fake_wcpt(rank, nranks, log, one_visible=False, slow_ranks=False):
         def buffer_free(self, b):
             pass
 
+        def buffer_download(self, b, n):
+            return np.full(n // 4, 0.25, np.float32).tobytes()
+
     class Group:
         def __init__(self, ctx, r):
             self.ctx, self.ranks, self.contexts, self.frames = ctx, [r], [ctx], 0
@@ -128,7 +131,7 @@ def _fake_wcpt(rank, nranks, log, one_visible=False, slow_ranks=False):
     return m
 
 
-def _rank_main(rank, world, port, out_dir, one_visible=False, settle_ms=0):
+def _rank_main(rank, world, port, out_dir, one_visible=False, settle_ms=0, mode=("--full", "--no-cpu-baseline")):
     sys.path[:0] = [ROOT, os.path.join(ROOT, "wc-path-tracer_amd")]
     os.environ.update(WORLD_SIZE=str(world), RANK=str(rank), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port - 1))
@@ -140,7 +143,7 @@ def _rank_main(rank, world, port, out_dir, one_visible=False, settle_ms=0):
     out = open(os.path.join(out_dir, f"rank{rank}.out"), "w")
     sys.stdout = out
     bench.main(["--gpus", str(world), "--config", "c1", "--steps", "3", "--warmup", "2", "--settle-ms", str(settle_ms),
-                "--no-cpu-baseline"])
+                *mode])
     out.close()
     json.dump([list(x) for x in log], open(os.path.join(out_dir, f"rank{rank}.log"), "w"))
 
@@ -188,6 +191,38 @@ def test_bench_one_process_per_gpu_plumbing(tmp_path, world, one_visible):
         assert ["set_output", 3, r == 0] in log                      # rgb payloads; only the root names a frame
         assert (["output", 256 * 256 * 12] in log) == (r == 0)         # c1: 256x256, rgb 12 B/px, on the root
         assert ["set_output", 0, False] in log                         # presenting off for the untimed re-render
+
+
+def test_plain_run_does_the_steps_and_nothing_more(tmp_path):
+    """Without --full a run renders its warmup and timed steps once (no untimed re-render for kernel times, presenting
+    never switched off), and its line holds the headline figure without the kernel time, the roofline or the CPU
+    baseline. --dump-outputs writes the frame the root presented after the last timed step, as float32."""
+    ctx = mproc.get_context("spawn")
+    port = _free_port()
+    world = 2
+    dump = tmp_path / "dump"
+    ps = [ctx.Process(target=_rank_main, args=(r, world, port, str(tmp_path), False, 0, ("--dump-outputs", str(dump))))
+          for r in range(world)]
+    for p in ps:
+        p.start()
+    for p in ps:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    d = json.loads([ln for ln in open(tmp_path / "rank0.out").read().splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["full"] is False
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Mray/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["segments_per_frame"] == 24 * (5 + 4)
+    for moved in ("kernel_ms_avg", "kernel_timing", "roofline", "per_rank_block_ms", "cpu_baseline", "speedup_vs_cpu"):
+        assert moved not in d
+    for r in range(world):
+        log = json.load(open(tmp_path / f"rank{r}.log"))
+        assert ["frames", 2 + 3] in log and ["set_output", 0, False] not in log
+    frame = np.load(dump / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (256, 256, 4)
+    assert d["dumped"] == {"frame": [256, 256, 4], "frame_nonfinite": [256, 256], "nonfinite_pixels": 0}
+    assert np.all(frame[..., :3] == 0.25) and np.all(frame[..., 3] == 1.0)   # the rgb payload, alpha restored
+    assert sorted(os.listdir(dump)) == ["frame.npy", "frame_nonfinite.npy"]
+    assert not np.load(dump / "frame_nonfinite.npy").any()
 
 
 def test_settle_phase_runs_the_same_frames_on_every_rank(tmp_path):

@@ -773,3 +773,25 @@ def test_group_sync_returns_device_lost_when_a_peer_skips_a_frame(gpu_ctx):
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["ok"] and all(d["checks"].values()), d["checks"]
     assert d["per_rank"][0]["sync_frame_3"]["rc"] == "WCPT_ERROR_DEVICE_LOST"
+
+
+def test_bench_dump_outputs_is_the_last_timed_frame(gpu_ctx, tmp_path):
+    """`python bench.py --gpus 1 --dump-outputs DIR`, a plain run: DIR/frame.npy is the frame after the last timed step
+    (c1: progressive frames 0..warmup+steps-1 of the Cornell box), bit for bit a context's render of the same frames;
+    the line holds the headline figure and none of what --full adds."""
+    import json
+    p = _run(["bench.py", "--gpus", "1", "--config", "c1", "--steps", "3", "--warmup", "2", "--settle-ms", "50",
+              "--dump-outputs", str(tmp_path / "out")], 120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["full"] is False and d["ms_per_step"] > 0 and d["value"] > 0
+    assert not {"kernel_ms_avg", "roofline", "cpu_baseline"} & set(d)
+    frame = np.load(tmp_path / "out" / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (256, 256, 4)
+    ref = _context_frames(get_scene("cornell"), 256, 256, range(5), bounces=1)
+    codes = np.load(tmp_path / "out" / "frame_nonfinite.npy")
+    assert np.isfinite(frame).all() and codes.shape == (256, 256)
+    assert np.array_equal(codes != 0, ~np.isfinite(ref).all(axis=2)) and d["dumped"]["nonfinite_pixels"] == (codes != 0).sum()
+    assert np.array_equal(frame.view(np.uint32), np.where(np.isfinite(ref), ref, np.float32(0)).view(np.uint32))

@@ -4,8 +4,8 @@
   reference recursion (oracle/pt_oracle.c, PathTracingRenderer.jai:147-217): identical node arrays and
   identical permuted index buffers, byte for byte.
 - OBJ: the product loader against the pure-Python restatement (oracle/obj_oracle.py, ModelLoader.jai:60-141)
-  on an edge-case fixture, on generated meshes and, when /root/reference is mounted (this container only),
-  on the reference's own asset OBJs. SURVEY.md Appendix B's mesh statistics pin the BVH sizes of those assets.
+  on an edge-case fixture, on generated meshes and on the reference's own asset OBJs (fixtures under
+  tests/golden/models). SURVEY.md Appendix B's mesh statistics pin the BVH sizes of those assets.
 """
 import os
 
@@ -18,7 +18,7 @@ import wcpt
 from wcpt import scene as wscene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF_MODELS = "/root/reference/run_tree/data/assets/models"
+REF_MODELS = os.path.join(HERE, "golden", "models")
 
 
 def _bvh_equal(mesh):
@@ -121,7 +121,6 @@ def test_obj_roundtrip_generated():
     assert np.array_equal(np.sort(tri_a.reshape(-1, 9), axis=0), np.sort(tri_b.reshape(-1, 9), axis=0))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference assets are mounted only in the build container")
 @pytest.mark.parametrize("fname,verts,indices,nodes,leaves,max_leaf", [
     # SURVEY.md Appendix B (a float64 restatement). The reference builds in f32 (Jai `float`), as we do:
     # mushroom and suzanita agree exactly; campfire has one extra split in f32 (161 nodes / 81 leaves

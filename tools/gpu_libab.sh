@@ -13,7 +13,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for cfg in ${CONFIGS:-c2}; do
     for lib in ${LIBS:-base cur}; do
       if [ "$lib" = "cur" ]; then unset WCPT_LIBRARY; else export WCPT_LIBRARY="wc-path-tracer_amd/variants/$lib.so"; fi
-      timeout -k 10 300 python3 bench.py --config $cfg --no-cpu-baseline --steps ${STEPS:-30} ${BENCH_ARGS:-} \
+      timeout -k 10 300 python3 bench.py --config $cfg --full --no-cpu-baseline --steps ${STEPS:-30} ${BENCH_ARGS:-} \
         > "$OUT/${cfg}_${lib}_$r.log" 2>&1 || { echo "bench $cfg $lib failed"; tail -5 "$OUT/${cfg}_${lib}_$r.log"; exit 1; }
       python3 - "$OUT/${cfg}_${lib}_$r.log" "$cfg" "$lib" <<'PY'
 import json, sys

@@ -32,7 +32,7 @@ for c in $CFGS; do
   base=${c%_orbit}; CAM=""; [ "$base" != "$c" ] && CAM="--camera orbit"
   CPU="--no-cpu-baseline"; [ "$c" = c2 ] && CPU=""
   EXTRA=""; [ "$c" = c4 ] && EXTRA="--steps 20 --warmup 3"
-  run bench_$c 900 python3 -u bench.py --config $base $CAM $CPU $EXTRA
+  run bench_$c 900 python3 -u bench.py --full --config $base $CAM $CPU $EXTRA
 done
 du -sh "$OUT"
 echo SESSION_DONE

@@ -8,7 +8,7 @@ for c in ${CONFIGS:-c2 ref c2_orbit ref_orbit c3 c4}; do
   base=${c%_orbit}; CAM=""; [ "$base" != "$c" ] && CAM="--camera orbit"
   CPU="--no-cpu-baseline"; [ "$c" = c2 ] && CPU=""
   EXTRA=""; [ "$c" = c4 ] && EXTRA="--steps 20 --warmup 3"
-  run bench_$c 900 python3 -u bench.py --config $base $CAM $CPU $EXTRA
+  run bench_$c 900 python3 -u bench.py --full --config $base $CAM $CPU $EXTRA
 done
-run bench_c2_driver_cmd 300 python3 -u bench.py --gpus 1 --steps 20 --warmup 5
+run bench_c2_driver_cmd 300 python3 -u bench.py --full --gpus 1 --steps 20 --warmup 5
 echo SESSION_DONE

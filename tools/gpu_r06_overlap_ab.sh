@@ -9,7 +9,7 @@ timeout -k 10 400 python3 -u -m pytest tests/test_gpu_overlap.py -x -q --timeout
 echo "rc=$rc"; tail -3 "$OUT/pytest.log"; [ $rc -eq 0 ] || exit 1
 line() {  # name, args...
   local n=$1; shift
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" > "$OUT/$n.json" 2> "$OUT/$n.err" || { echo "$n failed"; tail -5 "$OUT/$n.err"; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/$n.json" 2> "$OUT/$n.err" || { echo "$n failed"; tail -5 "$OUT/$n.err"; exit 1; }
   python3 -c "import json; d=json.loads(open('$OUT/$n.json').read().strip().splitlines()[-1]); print('$n', d['ms_per_step'], d['value'], d['kernel_ms_avg'])"
 }
 for r in ${ROUNDS:-1 2}; do

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 TAG=${TAG:-r06_s20b}; OUT=gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
 line() {
   local n=$1 lib=$2; shift 2
-  WCPT_LIBRARY=$lib timeout -k 10 200 python3 bench.py --no-cpu-baseline "$@" > "$OUT/$n.json" 2> "$OUT/$n.err" || { echo "$n failed"; tail -3 "$OUT/$n.err"; exit 1; }
+  WCPT_LIBRARY=$lib timeout -k 10 200 python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/$n.json" 2> "$OUT/$n.err" || { echo "$n failed"; tail -3 "$OUT/$n.err"; exit 1; }
   python3 -c "import json; d=json.loads(open('$OUT/$n.json').read().strip().splitlines()[-1]); print('$n', d['ms_per_step'], d['kernel_ms_avg'], d['build_id'])"
 }
 CUR=$PWD/wc-path-tracer_amd/libwcpt.so; OLD=$PWD/wc-path-tracer_amd/variants/pre_overlap.so
