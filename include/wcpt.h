@@ -145,6 +145,20 @@ extern "C" {
  * whose waves differ much in length: the reference's scene in an 8-way block 0.308 -> 0.260 ms, the Cornell box +0.9 %).
  * Same results. Added under ABI 4. */
 #define WCPT_OPTION_FRAME_OVERLAP 15
+/* Primary cache (megakernel). The primary ray of a pixel depends only on the pixel, the frame size, inverseProjection,
+ * inverseView and position -- no random number -- so while the camera and the scene stand still every progressive frame
+ * finds the primary Intersect record (t, primitive, draw) of the frame before. 1 (default): the first render after
+ * frame 0 of such a sequence stores each pixel's record (8 bytes per pixel with one draw command, 12 with several) and
+ * the renders that follow read it instead of tracing the primary segment; hit resolution and shading run as ever, from
+ * the current buffers. A render with renderedFramesCount == 0 drops the cache and renders plainly, so a camera that
+ * moves every frame pays nothing. The cache is also dropped when anything the record depends on changes: the camera's
+ * bytes, sphereCount, drawCommandCount, the frame size or the context's rows, the sphere or draw-command address, any
+ * wcpt_buffer_alloc / wcpt_buffer_upload / wcpt_buffer_free, an option change, or a render by the wavefront kernel.
+ * wcpt_render_counters never uses it. 0: off. It is active only while WCPT_OPTION_TRIANGLE_CACHE is 1, and it relies
+ * on the same promise, now extended to the sphere buffer: scene buffers change through wcpt_buffer_upload, or the
+ * application resets renderedFramesCount to 0 (as the reference's editor does whenever something moves).
+ * Same results. Added under ABI 4. */
+#define WCPT_OPTION_PRIMARY_CACHE 16
 
 /* ---- POD types with the reference byte layouts -------------------------------------------------- */
 
@@ -350,6 +364,9 @@ int      wcpt_composite(wcpt_context* ctx, uint64_t dst, int format);
 int      wcpt_render(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t materials,
                      uint64_t spheres, uint64_t draw_commands);
 int      wcpt_sync(wcpt_context* ctx);
+/* How many renders of the context stored (*writes) and read (*reads) the primary cache (WCPT_OPTION_PRIMARY_CACHE)
+ * since it was created; either pointer may be null. Host only. Added under ABI 4. */
+int      wcpt_primary_cache_stats(wcpt_context* ctx, uint64_t* writes, uint64_t* reads);
 /* Same frame through the instrumented kernel: counts the reference algorithm's work.
  * Does not write the image. Synchronous. */
 int      wcpt_render_counters(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t materials,

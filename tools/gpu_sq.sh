@@ -15,9 +15,14 @@ for cfg in ${CONFIGS:-c2 ref c3 c4}; do
   SETTLE=""; [ -n "$CAM" ] && SETTLE="--settle-ms 0 --steps 6 --warmup 0"
   B="--config $base $CAM --no-cpu-baseline --steps 2 --warmup 1 $SETTLE"
   [ "$cfg" = c4 ] && B="--config $cfg --no-cpu-baseline --steps 1 --warmup 0 --settle-ms 0"
+  # the still camera on the megakernel: the timed frames read the primary cache (WCPT_OPTION_PRIMARY_CACHE), a build of
+  # its own, while the settle phase repeats frame 0, which the plain build renders. Without the settle phase and over 60
+  # frames the counters average over one plain, one write and 62 read frames
+  MKSTILL=""; { [ "$cfg" = c2 ] || [ "$cfg" = ref ]; } && MKSTILL="--settle-ms 0"
+  [ -n "$MKSTILL" ] && B="--config $base --no-cpu-baseline --steps 60 --warmup 4 $MKSTILL"
   # the kernel-stats run is the bench line's own command (tools/gpu_r05_session.sh: default steps and warmup, c4 20 + 3),
   # so the rocprof average covers the same frames under the same sustained load as the bench's HIP events
-  PB=""; [ "$cfg" = c4 ] && PB="--steps 20 --warmup 3"
+  PB="$MKSTILL"; [ "$cfg" = c4 ] && PB="--steps 20 --warmup 3"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$cfg" -o $cfg -- python3 bench.py --config $base $CAM --no-cpu-baseline $PB > "$OUT/prof_$cfg.log" 2>&1 || { echo "prof $cfg failed"; tail -3 "$OUT/prof_$cfg.log"; exit 1; }
   echo "prof $cfg ok"
   n=0

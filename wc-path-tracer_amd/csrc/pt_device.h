@@ -1543,16 +1543,32 @@ __device__ __forceinline__ bool root_step(const Ray& ray, const DrawGeom& g, flo
 #ifndef WCPT_MK_PRIMARY_REUSE
 #define WCPT_MK_PRIMARY_REUSE 1
 #endif
-template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack>
+/* Primary cache (WCPT_OPTION_PRIMARY_CACHE): the same record kept from one frame to the next while camera, frame
+ * geometry and scene stand still (primary_cache_key.h has the rule). Render builds only; PC is the launch's mode:
+ * kPrimCacheWrite traces as usual and stores the lane's record after the primary segment of sample 0 at `pcache`
+ * (t bits, primitive word, and the draw when the frame has several: 2 or 3 u32 per pixel, tile-major -- record index
+ * (ty * tilesX + tx) * 64 + lane; `pcache` is the tile's first record, wave-uniform, so a wave touches one contiguous
+ * run whatever the tile order or pipe; a miss is (kInfinity, kNoPrim)); kPrimCacheRead resolves the primary segment of every sample from the record the caller loaded
+ * into prim_rec, and passes primary = false as a constant, so the primary-only leaf code (primary pair records, sign
+ * pre-reject) is not in that kernel at all. */
+constexpr int kPrimCacheNone = 0, kPrimCacheWrite = 1, kPrimCacheRead = 2;
+/* the lane's record among its tile's */
+template <bool SINGLE>
+__device__ __forceinline__ uint32_t* prim_cache_lane(uint32_t* tile_records)
+{
+    return tile_records + (threadIdx.x & 63u) * (SINGLE ? 2u : 3u);
+}
+template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, int PC = kPrimCacheNone>
 __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& sd, const wcpt_sphere* __restrict__ spheres,
                                          const wcpt_draw_command* __restrict__ draws,
                                          const uint64_t* __restrict__ tri_records, Stack& stk,
                                          Counters& cnt, bool& overflow, bool primary, float4& prim_rec,
-                                         bool reuse_primary)
+                                         bool reuse_primary, uint32_t* __restrict__ pcache = nullptr)
 {
     float rt = kInfinity;
     uint32_t prim = kNoPrim, primDraw = 0;
-    if (!COUNT && WCPT_MK_PRIMARY_REUSE && reuse_primary) { /* a later sample's primary segment (TraceRay) */
+    /* a later sample's primary segment, or under the primary cache's read mode every sample's (TraceRay) */
+    if (!COUNT && (WCPT_MK_PRIMARY_REUSE || PC == kPrimCacheRead) && reuse_primary) {
         rt = prim_rec.x;
         prim = __float_as_uint(prim_rec.y);
         primDraw = __float_as_uint(prim_rec.z);
@@ -1663,6 +1679,12 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
         }
     }
     if (!COUNT && WCPT_MK_PRIMARY_REUSE && primary && sd.samples > 1u) prim_rec = make_float4(rt, __uint_as_float(prim), __uint_as_float(primDraw), 0.0f);
+    if (!COUNT && PC == kPrimCacheWrite && primary && !reuse_primary) { /* a traced primary segment: sample 0's */
+        uint32_t* const pl = prim_cache_lane<SINGLE>(pcache);
+        pl[0] = __float_as_uint(rt);
+        pl[1] = prim;
+        if (!SINGLE) pl[2] = primDraw;
+    }
     if (COUNT && prim != kNoPrim) cnt.hits++;
     ref_segment_end<COUNT>(cnt);
     const Hit hit = resolve_hit(ray, rt, prim, primDraw, spheres, draws, tri_records);
@@ -1831,13 +1853,13 @@ __device__ __forceinline__ bool path_shade(PathState& ps, const Hit& h, uint32_t
 /* pathTracer.comp:241-284. prim_rec: the primary segment's Intersect record (t, primitive, draw), written by the
  * first sample; reuse_primary: a later sample, whose primary segment reads it instead of tracing the same ray again
  * (intersect). */
-template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, bool REUSE = false>
+template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, bool REUSE = false, int PC = kPrimCacheNone>
 __device__ __forceinline__ f3 TraceRay(Ray ray, uint32_t& rng, const wcpt_scene_data& sd,
                                        const wcpt_material* __restrict__ mats, const wcpt_sphere* __restrict__ spheres,
                                        const wcpt_draw_command* __restrict__ draws,
                                        const uint64_t* __restrict__ tri_records, Stack& stk,
                                        Counters& cnt, bool& overflow, bool lastSample, float4& prim_rec,
-                                       bool reuse_primary)
+                                       bool reuse_primary, uint32_t* __restrict__ pcache = nullptr)
 {
     PathState ps;
     path_begin(ps, ray.origin, ray.direction);
@@ -1845,8 +1867,13 @@ __device__ __forceinline__ f3 TraceRay(Ray ray, uint32_t& rng, const wcpt_scene_
     /* segment counter of this sample: uniform across the wave's lanes (all start a sample together), so `primary`
      * (segment 0: origin = the camera) is a wave-uniform branch condition */
     for (uint32_t seg = 0;; seg++) {
-        const Hit h = intersect<COUNT, DIAG, PAIRS, SINGLE>(ps.ray, sd, spheres, draws, tri_records, stk, cnt, overflow,
-                                                           seg == 0u, prim_rec, REUSE && seg == 0u && reuse_primary);
+        /* primary-cache read: no segment is traced as a primary one, and segment 0 of every sample is the record's */
+        const bool primary = PC != kPrimCacheRead && seg == 0u;
+        const bool reuse = PC == kPrimCacheRead ? seg == 0u : REUSE && seg == 0u && reuse_primary;
+        /* the sample-reuse build keeps the record in prim_rec anyway: its write is the caller's, after sample 0 */
+        constexpr int PCI = (PC == kPrimCacheWrite && REUSE) ? kPrimCacheNone : PC;
+        const Hit h = intersect<COUNT, DIAG, PAIRS, SINGLE, Stack, PCI>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
+                                                                      overflow, primary, prim_rec, reuse, pcache);
         const bool done = path_shade(ps, h, rng, sd, mats, L, lastSample);
         phase_mark(cnt, 5);
         if (done) return L;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/wcpt.h"
+#include "primary_cache_key.h"
 #include "row_map.h"
 
 namespace wcpt {
@@ -50,6 +51,8 @@ struct LaunchArgs {
     const uint64_t* tri_records_pipe1 = nullptr;
     hipError_t (*pipe1_prepare)(void* user, hipStream_t stream) = nullptr;
     void* pipe1_user = nullptr;
+    /* primary cache (MkState, primary_cache_key.h): this render's key, or null when the cache is off for it */
+    const PrimaryCacheKey* prim_key = nullptr;
 };
 
 /* Wavefront path state (pt_wavefront.hip): structure-of-arrays in one device allocation. */
@@ -154,6 +157,16 @@ struct MkState {
     hipStream_t pipe[2] = {};  /* [1]: pipe 1's stream (pipe 0 runs on the context's stream) */
     hipEvent_t fork = nullptr;
     hipEvent_t join[2] = {};
+    /* Primary cache (WCPT_OPTION_PRIMARY_CACHE): per pixel of the context's rows the primary segment's Intersect record
+     * -- 8 B (t, primitive word) when the frame has one draw command, 12 B (+ draw) otherwise; a miss is (kInfinity,
+     * kNoPrim) -- tile-major like the costs above: record (ty * tilesX + tx) * 64 + lane. Written by the first render
+     * after frame 0 of a still camera and read by the renders that follow while prim_key stands (primary_cache_key.h).
+     * Independent of the kernel that fills it. */
+    void* prim_mem = nullptr;
+    uint64_t prim_bytes = 0;
+    bool prim_valid = false;
+    PrimaryCacheKey prim_key = {};
+    uint64_t prim_writes = 0, prim_reads = 0; /* renders that took each instantiation (wcpt_primary_cache_stats) */
 };
 constexpr uint32_t kMkPipes = 2;
 void mk_release(MkState& mk);

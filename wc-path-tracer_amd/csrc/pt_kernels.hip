@@ -8,6 +8,8 @@
  * Instantiations: COUNT=false renders; COUNT=true runs the same frame without writing the image and counts the
  * reference algorithm's work; DIAG=true additionally counts SIMD lane/wave steps with a
  * __ballot inside the traversal loop (tools/diag.py only — kept out of the COUNT build the parity tests use).
+ * The render builds come in three primary-cache modes (PC; pt_device.h intersect, primary_cache_key.h): none, write
+ * (stores each pixel's primary Intersect record) and read (resolves the primary segment from it).
  */
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -64,14 +66,15 @@ __device__ __forceinline__ void tile_of_block(uint32_t tilesX, uint32_t tilesTot
 }
 
 /* Shade one pixel (pathTracer.comp:290-323) with the given traversal stack. */
-template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, bool REUSE, class Stack>
+template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, bool REUSE, int PC, class Stack>
 __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcpt_material* __restrict__ mats,
                                             const wcpt_sphere* __restrict__ spheres,
                                             const wcpt_draw_command* __restrict__ draws,
                                             const uint64_t* __restrict__ tri_records, float4* __restrict__ image,
                                             float* __restrict__ wire, uint32_t wire_ch,
                                             uint32_t W, uint32_t H, const RowMap& rm, const RowMap& wm, uint32_t lx,
-                                            uint32_t ly, Stack& stk, Counters& cnt, bool& overflow)
+                                            uint32_t ly, Stack& stk, Counters& cnt, bool& overflow,
+                                            uint32_t* __restrict__ pcache)
 {
     const uint32_t x = lx, y = frame_row(rm, ly); /* the frame row: a row block or interleaved stripes (row_map.h) */
     const f3 dir = primary_direction(sd, x, y, W, H);
@@ -86,13 +89,28 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
     f3 result = mk3(0.0f, 0.0f, 0.0f);
     const f3 origin = mk3(sd.position[0], sd.position[1], sd.position[2]);
     float4 prim_rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f); /* sample 0's primary Intersect record */
-    for (uint32_t s = 0; s < sd.samples; s++) { /* :309-310, all samples share the primary ray */
+    if constexpr (PC == kPrimCacheRead) { /* ... as an earlier frame stored it: loaded beside the image read */
+        const uint32_t* const pl = prim_cache_lane<SINGLE>(pcache);
+        prim_rec.x = __uint_as_float(pl[0]);
+        prim_rec.y = __uint_as_float(pl[1]);
+        if (!SINGLE) prim_rec.z = __uint_as_float(pl[2]);
+    }
+    /* the one-sample read build (launch_mega_render) has its sample count as a constant: the record then dies at its one
+     * use instead of staying live across a sample loop (intersect: 20 VGPRs) */
+    const uint32_t samples = (PC == kPrimCacheRead && !REUSE) ? 1u : sd.samples;
+    for (uint32_t s = 0; s < samples; s++) { /* :309-310, all samples share the primary ray */
         Ray r;
         r.origin = origin;
         r.direction = dir;
         r.invDirection = rcp3(dir);
-        result = result + TraceRay<COUNT, DIAG, PAIRS, SINGLE, Stack, REUSE>(r, seed, sd, mats, spheres, draws, tri_records, stk, cnt, overflow,
-                                                       s + 1u == sd.samples, prim_rec, s > 0u);
+        result = result + TraceRay<COUNT, DIAG, PAIRS, SINGLE, Stack, REUSE, PC>(r, seed, sd, mats, spheres, draws, tri_records, stk, cnt, overflow,
+                                                       s + 1u == samples, prim_rec, s > 0u, pcache);
+    }
+    if (PC == kPrimCacheWrite && REUSE) { /* this build (samples > 1) holds sample 0's record in prim_rec (TraceRay) */
+        uint32_t* const pl = prim_cache_lane<SINGLE>(pcache);
+        pl[0] = __float_as_uint(prim_rec.x);
+        pl[1] = __float_as_uint(prim_rec.y);
+        if (!SINGLE) pl[2] = __float_as_uint(prim_rec.z);
     }
     result = result / (float)sd.samples; /* :312 */
     if (!COUNT) {
@@ -117,7 +135,7 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
 #ifndef WCPT_MK_WAVES
 #define WCPT_MK_WAVES 1
 #endif
-template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE>
+template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE, int PC>
 __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_scene_data sd, const wcpt_material* __restrict__ mats,
                                                     const wcpt_sphere* __restrict__ spheres,
                                                     const wcpt_draw_command* __restrict__ draws,
@@ -127,7 +145,8 @@ __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_sc
                                                     const RowMap wm, uint32_t rows, uint32_t tilesX, uint32_t tilesTotal,
                                                     uint32_t scatter, const uint32_t* __restrict__ tile_order,
                                                     uint32_t* __restrict__ tile_cost, uint32_t* __restrict__ status,
-                                                    unsigned long long* __restrict__ counters)
+                                                    unsigned long long* __restrict__ counters,
+                                                    uint32_t* __restrict__ prim_cache)
 {
     const uint64_t c0 = (!COUNT && tile_cost) ? __builtin_amdgcn_s_memtime() : 0ull;
     uint32_t tx, ty;
@@ -137,21 +156,24 @@ __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_sc
     Counters cnt = {};
     phase_start(cnt);
     bool overflow = false;
+    /* the tile's primary-cache records (pt_device.h prim_cache_lane): wave-uniform, the lane's offset is added at the use */
+    uint32_t* const pcache = PC == kPrimCacheNone ? nullptr
+        : prim_cache + (size_t)(ty * tilesX + tx) * (64u * (SINGLE ? 2u : 3u));
     if (lx < W && ly < rows) {
         if constexpr (SK == 0) {
             uint64_t mem[kPrivateStack];
             PrivateStack<kPrivateStack> stk;
             stk.mem = (priv_u64_ptr)mem;
-            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
-                                            cnt, overflow);
+            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE, PC>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
+                                            cnt, overflow, pcache);
         } else {
             __shared__ uint64_t s_stack[kLdsStack * 64];
             uint64_t spill[kSpillStack];
             LdsStack<kLdsStack, kSpillStack> stk;
             stk.base = (lds_u64_ptr)(s_stack + (threadIdx.x & 63u));
             stk.spill = (priv_u64_ptr)spill;
-            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
-                                            cnt, overflow);
+            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE, PC>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
+                                            cnt, overflow, pcache);
         }
     }
     if (overflow) atomicOr(status, 1u);
@@ -415,7 +437,9 @@ hipError_t launch_build_primary_pairs(const void* pairs, uint32_t npairs, float 
 
 /* list / grid: a frame-overlap pipe's share of the cost-ordered tiles (MkState::split); null: every tile, in the order
  * below */
-template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE = false>
+static_assert(dev::kPrimCacheNone == kPrimaryCacheNone && dev::kPrimCacheWrite == kPrimaryCacheWrite &&
+                  dev::kPrimCacheRead == kPrimaryCacheRead, "primary-cache modes");
+template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE = false, int PC = kPrimaryCacheNone>
 static hipError_t launch_mega(const LaunchArgs& a, MkState& mk, hipStream_t stream, uint32_t tilesX, uint32_t tiles,
                               const uint32_t* list, uint32_t grid)
 {
@@ -438,10 +462,11 @@ static hipError_t launch_mega(const LaunchArgs& a, MkState& mk, hipStream_t stre
      * a sort (launch_megakernel) take the tiles longest first */
     const bool cost_order = !COUNT && a.mk_tile_order == 2 && mk.cost != nullptr;
     const uint32_t* order = list ? list : (cost_order && mk.order_valid ? mk.order : nullptr);
-    hipLaunchKernelGGL((dev::pt_megakernel<COUNT, DIAG, SK, PAIRS, SINGLE, REUSE>), dim3(list ? grid : tiles), dim3(64), 0,
+    hipLaunchKernelGGL((dev::pt_megakernel<COUNT, DIAG, SK, PAIRS, SINGLE, REUSE, PC>), dim3(list ? grid : tiles), dim3(64), 0,
                        stream, a.sd, a.materials, a.spheres, a.draws, a.tri_records, a.image, a.wire, a.wire_ch, a.W, a.H,
                        RowMap{a.y0, a.row_shift, a.row_gap}, a.wire_rows, a.rows, tilesX, tiles, scatter, order,
-                       cost_order ? mk.cost : nullptr, a.status, a.counters);
+                       cost_order ? mk.cost : nullptr, a.status, a.counters,
+                       PC != kPrimaryCacheNone ? static_cast<uint32_t*>(mk.prim_mem) : nullptr);
     return hipGetLastError();
 }
 
@@ -466,6 +491,7 @@ void mk_release(MkState& mk)
     }
     if (mk.fork) (void)hipEventDestroy(mk.fork);
     if (mk.mem) (void)hipFree(mk.mem);
+    if (mk.prim_mem) (void)hipFree(mk.prim_mem);
     const int cus = mk.cus;
     mk = MkState{};
     mk.cus = cus;
@@ -546,22 +572,35 @@ static hipError_t cost_order_sort(MkState& mk, uint32_t tiles, hipStream_t strea
     return e;
 }
 
+/* the render instantiations: sample reuse (samples > 1) x primary-cache mode of this render */
+template <int SK, bool PAIRS, bool SINGLE>
+static hipError_t launch_mega_render(const LaunchArgs& a, int pcmode, MkState& mk, hipStream_t stream, uint32_t tilesX,
+                                     uint32_t tiles, const uint32_t* list, uint32_t grid)
+{
+    const bool reuse = a.sd.samples > 1u && WCPT_MK_PRIMARY_REUSE;
+    if (pcmode == kPrimaryCacheRead) /* its one-sample form holds the sample count as a constant: only for samples == 1 */
+        return a.sd.samples != 1u
+                   ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheRead>(a, mk, stream, tilesX, tiles, list, grid)
+                   : launch_mega<false, false, SK, PAIRS, SINGLE, false, kPrimaryCacheRead>(a, mk, stream, tilesX, tiles, list, grid);
+    if (pcmode == kPrimaryCacheWrite)
+        return reuse ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheWrite>(a, mk, stream, tilesX, tiles, list, grid)
+                     : launch_mega<false, false, SK, PAIRS, SINGLE, false, kPrimaryCacheWrite>(a, mk, stream, tilesX, tiles, list, grid);
+    return reuse ? launch_mega<false, false, SK, PAIRS, SINGLE, true>(a, mk, stream, tilesX, tiles, list, grid)
+                 : launch_mega<false, false, SK, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
+}
+
+/* pcmode: the render's primary-cache mode (the COUNT / DIAG builds never read or write the cache: their counters are
+ * the reference's) */
 template <bool PAIRS, bool SINGLE>
-static hipError_t launch_mega_sk(const LaunchArgs& a, int mode, int stack_kind, MkState& mk, hipStream_t stream,
+static hipError_t launch_mega_sk(const LaunchArgs& a, int mode, int stack_kind, int pcmode, MkState& mk, hipStream_t stream,
                                  uint32_t tilesX, uint32_t tiles, const uint32_t* list = nullptr, uint32_t grid = 0)
 {
     if (stack_kind == 0) {
-        if (mode == kModeRender)
-            return a.sd.samples > 1u && WCPT_MK_PRIMARY_REUSE
-                       ? launch_mega<false, false, 0, PAIRS, SINGLE, true>(a, mk, stream, tilesX, tiles, list, grid)
-                       : launch_mega<false, false, 0, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
+        if (mode == kModeRender) return launch_mega_render<0, PAIRS, SINGLE>(a, pcmode, mk, stream, tilesX, tiles, list, grid);
         if (mode == kModeCount) return launch_mega<true, false, 0, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
         return launch_mega<true, true, 0, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
     }
-    if (mode == kModeRender)
-        return a.sd.samples > 1u && WCPT_MK_PRIMARY_REUSE
-                   ? launch_mega<false, false, 1, PAIRS, SINGLE, true>(a, mk, stream, tilesX, tiles, list, grid)
-                   : launch_mega<false, false, 1, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
+    if (mode == kModeRender) return launch_mega_render<1, PAIRS, SINGLE>(a, pcmode, mk, stream, tilesX, tiles, list, grid);
     if (mode == kModeCount) return launch_mega<true, false, 1, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
     return launch_mega<true, true, 1, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
 }
@@ -622,12 +661,42 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
     }
     /* one draw command (the reference's case): the single-draw instantiation, without the draw loop */
     const bool single = a.sd.drawCommandCount == 1u;
+    /* Primary cache (primary_cache_key.h has the rule). Counting runs leave it as it is. A write needs no join of its
+     * own, and neither does the read that follows it: a pixel belongs to the same pipe while the tile order stands, and
+     * every re-sort, new geometry or other kernel joins both pipes into the stream first (above and below), so the
+     * write of frame n is ordered before the read of frame n + 1 by the rule that orders the image's read-modify-write.
+     * The step from unpiped to piped launches keeps it too: the fork event is recorded on the stream behind the
+     * unpiped write, and pipe 1 waits for it before its first read. */
+    int pcmode = kPrimaryCacheNone;
+    if (mode == kModeRender) {
+        const PrimaryCacheKey none = {};
+        pcmode = primary_cache_decide(a.prim_key != nullptr, a.sd.renderedFramesCount, mk.prim_valid, mk.prim_key,
+                                      a.prim_key ? *a.prim_key : none);
+        if (pcmode == kPrimaryCacheNone) mk.prim_valid = false;
+    }
+    if (pcmode == kPrimaryCacheWrite) {
+        mk.prim_valid = false;
+        const uint64_t bytes = (uint64_t)tiles * 64ull * (single ? 8ull : 12ull);
+        if (bytes > mk.prim_bytes) { /* grows like mk.mem: behind everything that may still read the old one */
+            if (mk.prim_mem) {
+                e = mk_join(mk, stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(stream);
+                if (e != hipSuccess) return e;
+                (void)hipFree(mk.prim_mem);
+                mk.prim_mem = nullptr;
+                mk.prim_bytes = 0;
+            }
+            e = hipMalloc(&mk.prim_mem, bytes);
+            if (e != hipSuccess) return e;
+            mk.prim_bytes = bytes;
+        }
+    }
     auto launch = [&](const LaunchArgs& la, hipStream_t s, const uint32_t* list, uint32_t grid) {
         if (la.pair_records)
-            return single ? launch_mega_sk<true, true>(la, mode, stack_kind, mk, s, tilesX, tiles, list, grid)
-                          : launch_mega_sk<true, false>(la, mode, stack_kind, mk, s, tilesX, tiles, list, grid);
-        return single ? launch_mega_sk<false, true>(la, mode, stack_kind, mk, s, tilesX, tiles, list, grid)
-                      : launch_mega_sk<false, false>(la, mode, stack_kind, mk, s, tilesX, tiles, list, grid);
+            return single ? launch_mega_sk<true, true>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid)
+                          : launch_mega_sk<true, false>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid);
+        return single ? launch_mega_sk<false, true>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid)
+                      : launch_mega_sk<false, false>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid);
     };
     if (pipes) {
         if (!mk.pending) { /* fork: pipe 1 after everything queued on the context's stream */
@@ -653,6 +722,13 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
         }
     } else {
         e = launch(a, stream, nullptr, 0);
+    }
+    if (e == hipSuccess && pcmode == kPrimaryCacheWrite) {
+        mk.prim_key = *a.prim_key;
+        mk.prim_valid = true;
+        mk.prim_writes++;
+    } else if (e == hipSuccess && pcmode == kPrimaryCacheRead) {
+        mk.prim_reads++;
     }
     if (e != hipSuccess || !cost_order) return e;
     /* sorted after renders 1, 4 and 16 of a geometry (the running averages settle), then every kResortEvery; the sort

@@ -159,6 +159,7 @@ struct wcpt_context {
     int sort_rays = 0;                 /* WCPT_OPTION_SORT_RAYS (wavefront only; measured a net loss on c3) */
     int wf_stack = 10;                 /* WCPT_OPTION_WF_STACK: LDS stack entries of the wavefront trace kernel */
     int tri_cache = 1;                 /* WCPT_OPTION_TRIANGLE_CACHE */
+    int prim_cache = 1;                /* WCPT_OPTION_PRIMARY_CACHE (active only with tri_cache) */
     int packed_refs = 1;               /* WCPT_OPTION_PACKED_REFS */
     int wf_fetch = -1;                 /* WCPT_OPTION_WF_FETCH */
     int wf_persist = -1;               /* WCPT_OPTION_WF_PERSIST */
@@ -744,9 +745,19 @@ int render_common(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t mate
                 "hipMemsetAsync(timers)");
 #endif
     hipError_t e = hipSuccess;
+    /* primary cache (primary_cache_key.h): the key of this render; launch_megakernel applies the rule. Under the
+     * triangle cache's promise only -- scene buffers change through wcpt_buffer_upload (which bumps the generation) or
+     * the application restarts accumulation at frame 0 -- so never with WCPT_OPTION_TRIANGLE_CACHE = 0. */
+    wcpt::PrimaryCacheKey pkey;
+    if (mode == wcpt::kModeRender && ctx->prim_cache && ctx->tri_cache) {
+        pkey = wcpt::primary_cache_key(*scene, a.W, a.H, a.y0, a.rows, a.row_shift, a.row_gap, spheres, draws,
+                                       reinterpret_cast<uint64_t>(a.tri_records), a.pair_records, ctx->generation);
+        a.prim_key = &pkey;
+    }
     switch (ctx->kernel_run) {
     case WCPT_KERNEL_MEGAKERNEL: e = wcpt::launch_megakernel(a, mode, ctx->stack_kind, ctx->mk, ctx->stream, overlap); break;
     case WCPT_KERNEL_WAVEFRONT:
+        if (mode == wcpt::kModeRender) ctx->mk.prim_valid = false; /* a frame the megakernel did not render */
         e = wcpt::launch_wavefront(a, mode, ctx->wf, ctx->wf_pipes, ctx->sort_rays != 0, ctx->wf_stack, ctx->stream, overlap);
         break;
     default: return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "kernel variant %d not available", ctx->kernel_run);
@@ -1066,6 +1077,11 @@ int wcpt_set_option(wcpt_context* ctx, int option, int value)
         return WCPT_SUCCESS;
     case WCPT_OPTION_TRIANGLE_CACHE:
         ctx->tri_cache = value ? 1 : 0;
+        ctx->generation++;
+        return WCPT_SUCCESS;
+    case WCPT_OPTION_PRIMARY_CACHE:
+        if (value < 0 || value > 1) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "primary cache %d", value);
+        ctx->prim_cache = value;
         ctx->generation++;
         return WCPT_SUCCESS;
     case WCPT_OPTION_WF_STACK:
@@ -1396,6 +1412,14 @@ int wcpt_render(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t materi
                 uint64_t draw_commands)
 {
     return render_common(ctx, scene, materials, spheres, draw_commands, wcpt::kModeRender);
+}
+
+int wcpt_primary_cache_stats(wcpt_context* ctx, uint64_t* writes, uint64_t* reads)
+{
+    if (!ctx) return set_error(nullptr, WCPT_ERROR_INVALID_HANDLE, "null context");
+    if (writes) *writes = ctx->mk.prim_writes;
+    if (reads) *reads = ctx->mk.prim_reads;
+    return WCPT_SUCCESS;
 }
 
 int wcpt_sync(wcpt_context* ctx)

@@ -57,6 +57,7 @@ OPTION_WF_FETCH = 12
 OPTION_WF_PERSIST = 13
 OPTION_GATHER_FRAME_ROWS = 14
 OPTION_FRAME_OVERLAP = 15
+OPTION_PRIMARY_CACHE = 16
 DEFAULT_WF_PIPES = 0  # wcpt_runtime.hip: by queue length (2 or 3)
 
 # gather payload formats (wcpt_set_gather_output, wcpt_group_set_output)
@@ -173,6 +174,7 @@ _PROTOTYPES = {
     "wcpt_composite": (_i, [_p, _u64, _i]),
     "wcpt_render": (_i, [_p, _p, _u64, _u64, _u64]),
     "wcpt_sync": (_i, [_p]),
+    "wcpt_primary_cache_stats": (_i, [_p, C.POINTER(_u64), C.POINTER(_u64)]),
     "wcpt_render_counters": (_i, [_p, _p, _u64, _u64, _u64, C.POINTER(Counters)]),
     "wcpt_read_diagnostics": (_i, [_p, C.POINTER(C.c_uint64), _u32]),
     "wcpt_profile_begin": (_i, [_p]),

@@ -157,6 +157,12 @@ class Context:
     def sync(self):
         self._chk(lib.wcpt_sync(self.h))
 
+    def primary_cache_stats(self) -> tuple:
+        """(writes, reads): the renders that stored / read the primary cache (WCPT_OPTION_PRIMARY_CACHE)."""
+        w, r = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib.wcpt_primary_cache_stats(self.h, C.byref(w), C.byref(r)))
+        return int(w.value), int(r.value)
+
     def render_counters(self, sd: np.ndarray, materials: int, spheres: int, draws: int,
                         diagnostics: bool = False) -> dict:
         """Reference-algorithm work counters of one frame (COUNTER_FIELDS); with diagnostics=True also the
