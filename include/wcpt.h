@@ -160,6 +160,42 @@ extern "C" {
  * Same results. Added under ABI 4. */
 #define WCPT_OPTION_PRIMARY_CACHE 16
 
+/* ---- options that change results (wcpt_set_option) ---------------------------------------------------------- */
+/* Arithmetic of the megakernel's render launches. WCPT_ARITH_EXACT (0, default): the reference's operand order, unfused,
+ * with correctly rounded reciprocal and square root and the deterministic software log / cos -- bit-identical to the
+ * CPU oracle. WCPT_ARITH_FAST (1) is a permission for a host that renders for display: megakernel render launches then
+ * take the fast instances, which relax
+ *   - the dot and cross products of the triangle tests and of the shading arithmetic (reflect, refract, the Fresnel
+ *     term, normalize, p + t * d) to fused multiply-adds, written out in the source -- the library is still built
+ *     without floating-point contraction, so which products fuse is defined, not chosen by the compiler. The sphere
+ *     test keeps its unfused products (its discriminant is cancellation-dominated on a large sphere, and fusing it
+ *     tripled the diverged pixels of the reference's scene) and takes only the hardware sqrt;
+ *   - 1/x and vector / scalar to the hardware reciprocal (v_rcp_f32, 1 ULP) and sqrt to v_sqrt_f32 (1 ULP);
+ *   - RandomValueNormalDistribution's log to v_log_f32 x ln 2 and its cos(2 pi u) to v_cos_f32(u).
+ * Unchanged: the PCG random stream, every integer decision, the traversal order, the slab test, exp in the absorption
+ * term, the primary ray, the frame accumulation, and the display step of WCPT_PAYLOAD_DISPLAY_RGBA8 (the exact function
+ * of the accumulated value). These always run exact, whatever the option says, and wcpt_last_arith then reports 0: the
+ * wavefront kernels (also when WCPT_KERNEL_AUTO resolves to them), wcpt_render_counters (it counts the reference
+ * algorithm's work), the diagnostics modes and wcpt_composite.
+ * What to expect, compared with the exact mode (= the CPU oracle) on the same inputs: a fast image is deterministic -- the
+ * same bits for the same frame on every tile order, stack kind, row split, frame overlap, primary-cache state and group
+ * layout, fast against fast -- and per pixel either close to the exact one (every channel within 1e-5 * max(1, |exact|))
+ * or diverged, where a rounding difference flipped a hit, a refraction or a take and the path went elsewhere. Stated
+ * tolerance, checked by tests/test_gpu_arith.py on the Cornell box, the dielectric and the reference's scenes: at most
+ * 0.5 % of a frame's pixels diverge, the median of |fast - exact| / max(1, |exact|) over all channels is <= 1e-6, and
+ * finiteness matches. Measured on the MI355X: 0.06-0.26 % of the pixels diverged on those cases, 0.008 % of a 1920x1080
+ * Cornell frame and 0.36 % of the reference's scene at 1920x1080; median 0 (more than half the values are bit-equal);
+ * DESIGN.md section 4 has the tables. The thresholds of the exact mode (99.9 % of the
+ * pixels within 1e-5, mean <= 1e-4) do not hold: a CPU oracle rebuilt with contraction allowed misses them too.
+ * Any other value returns WCPT_ERROR_INVALID_ARGUMENT and leaves the option as it was. Accepting a value restarts the
+ * cached frame preparation and drops the primary cache (a cached record belongs to the arithmetic that found it); an
+ * application should also restart accumulation (renderedFramesCount = 0) unless it wants frames of both kinds blended.
+ * In a group the option is set per rank (wcpt_group_context); all ranks must set the same value, or the presented
+ * frame mixes rows of both kinds. Added under ABI 4. */
+#define WCPT_OPTION_ARITH 17
+#define WCPT_ARITH_EXACT 0
+#define WCPT_ARITH_FAST  1
+
 /* ---- POD types with the reference byte layouts -------------------------------------------------- */
 
 /* SceneData — pathTracer.comp:10-22 == PathTracingRenderer.jai:38-51. 164 bytes.
@@ -301,6 +337,9 @@ int         wcpt_set_stream(wcpt_context* ctx, void* hip_stream);  /* NULL: the 
 int         wcpt_set_kernel(wcpt_context* ctx, int variant);       /* WCPT_KERNEL_*                       */
 int         wcpt_last_kernel(wcpt_context* ctx, int* variant);     /* what the last render ran (AUTO resolved) */
 int         wcpt_set_option(wcpt_context* ctx, int option, int value); /* WCPT_OPTION_*                   */
+/* The arithmetic the last wcpt_render really ran (WCPT_ARITH_*): WCPT_ARITH_FAST only after a megakernel render with
+ * WCPT_OPTION_ARITH set to it; 0 before any render. Host only. Added under ABI 4. */
+int         wcpt_last_arith(wcpt_context* ctx, int* arith);
 
 /* ---- device buffers (BufferManager.jai) ------------------------------------------------------------ */
 int      wcpt_buffer_alloc(wcpt_context* ctx, uint64_t bytes, wcpt_buffer* out);
@@ -547,7 +586,10 @@ void     wcpt_string_free(char* text);
  * 14 = the two triangle acceptance forms on (u, v) = (in, in2) with t = 1 (bit 0 compares, bit 1 minimum3),
  * 15 = as 8 for the kernels' square root (sqrt_exact) against the correctly rounded sqrtf,
  * 16 = the kernels' GLSL vector / scalar on one component: in * RN(1 / in2), 17 = as 8 for the integer form of the
- * triangle take (0 < t < rec.t as bits(t) - 1 < bits(rec.t) - 1) with rec.t = in2[i]. Host arrays of 32-bit words. */
+ * triangle take (0 < t < rec.t as bits(t) - 1 < bits(rec.t) - 1) with rec.t = in2[i].
+ * The fast arithmetic mode's functions (WCPT_OPTION_ARITH), to be compared with fn 2, 3, 5, 9 and 7: 18 = log
+ * (v_log_f32 x ln 2), 19 = cos(2 pi u) given u (v_cos_f32), 20 = sqrt (v_sqrt_f32), 21 = the reciprocal (v_rcp_f32),
+ * 22 = RandomDirection (3 per input). Host arrays of 32-bit words. */
 int      wcpt_selftest_device(wcpt_context* ctx, int fn, const uint32_t* in, const uint32_t* in2,
                               uint32_t* out, uint32_t n);
 

@@ -3,8 +3,11 @@
     python tools/ab.py --config c3 --variants "kernel=0" "kernel=2" "kernel=2,deindex=1" [--frames 5 --rounds 3]
 
 Each variant is a comma list of option=value: stack=<0|1>, kernel=<0|2>, order=<0|1|2>, pipes=<1..4>, deindex=<0|1> (mesh re-laid out in
-BVH leaf order with identity indices: same triangles, same results, soup-like locality). Prints the median
-ms/frame (HIP events on the context stream) and Mray/s.
+BVH leaf order with identity indices: same triangles, same results, soup-like locality), arith=<0|1> (WCPT_OPTION_ARITH:
+1 = the megakernel's fast-arithmetic instances). Prints the median ms/frame (HIP events on the context stream) and
+Mray/s. With --check, variants of the same arith are compared bit for bit; variants of different arith by the
+statistics of the fast mode's stated tolerance (wcpt.h WCPT_OPTION_ARITH): diverged pixels (some channel off by more than
+1e-5 * max(1, |ref|), or a finiteness mismatch), the median relative difference, mean |d| and the bit-equal share.
 """
 import argparse
 import os
@@ -25,6 +28,18 @@ import bench  # noqa: E402  (CONFIGS)
 
 def parse(spec):
     return dict(kv.split("=") for kv in filter(None, spec.split(",")))
+
+
+def arith_stats(img, ref):
+    """img, ref: float32 [H, W, 4] -> (diverged pixels, median relative difference, mean |d|, bit-equal pixels)"""
+    a, b = img.astype(np.float64), ref.astype(np.float64)
+    fin = np.isfinite(a) & np.isfinite(b)
+    d = np.where(fin, np.abs(np.where(fin, a, 0.0) - np.where(fin, b, 0.0)), 0.0)
+    rel = d / np.maximum(1.0, np.where(fin, np.abs(b), 1.0))
+    same_class = fin | ((np.isfinite(a) == np.isfinite(b)) & (np.isnan(a) == np.isnan(b)))
+    diverged = ((rel > 1e-5) | ~same_class).any(axis=-1)
+    equal = (img.view(np.uint32) == ref.view(np.uint32)).all(axis=-1)
+    return int(diverged.sum()), float(np.median(rel)), float(d.mean()), int(equal.sum())
 
 
 def deindexed(s):
@@ -71,6 +86,7 @@ def main():
             ctx.set_option(wcpt._lib.OPTION_WF_REFILL, int(o.get("refill", wcpt._lib.DEFAULT_WF_REFILL)))
             ctx.set_option(wcpt._lib.OPTION_MK_TILE_ORDER, int(o.get("order", 2)))
             ctx.set_option(wcpt._lib.OPTION_WF_PIPES, int(o.get("pipes", wcpt._lib.DEFAULT_WF_PIPES)))
+            ctx.set_option(wcpt._lib.OPTION_ARITH, int(o.get("arith", 0)))
             dev = scenes[o.get("deindex", "0")]
             ctx.profile_begin()
             for sd in sds:
@@ -81,13 +97,21 @@ def main():
                 res[v].append(ms / n)
             if a.check and r == a.rounds:
                 imgs[v] = ctx.readback(a.rows or H).view(np.uint32).copy()
-    print(f"{a.config}: {desc}; {segs / a.frames:.0f} segments/frame")
+    print(f"{a.config}: {desc}; {segs / a.frames:.0f} segments/frame; wcpt_build_id {wcpt.lib.wcpt_build_id().decode()}")
     for v, t in res.items():
         m = statistics.median(t)
-        print(f"  {v:30s} {m:8.3f} ms/frame  {segs / a.frames / m / 1e3:9.1f} Mray/s   (runs {', '.join(f'{x:.3f}' for x in t)})")
+        print(f"  {v:30s} {m:8.3f} ms/frame  {segs / a.frames / m / 1e3:9.1f} Mray/s   spread {min(t):.3f}-{max(t):.3f}"
+              f"   (runs {', '.join(f'{x:.3f}' for x in t)})")
     if imgs:
         first = next(iter(imgs.values()))
         for v, im in imgs.items():
+            if parse(v).get("arith", "0") != parse(a.variants[0]).get("arith", "0"):
+                n, med, mean, eq = arith_stats(im.view(np.float32), first.view(np.float32))
+                px = im.shape[0] * im.shape[1]
+                print(f"  image of {v}: other arithmetic than {a.variants[0]}: {n} / {px} pixels diverged "
+                      f"({100.0 * n / px:.3f} %), median rel {med:.3g}, mean |d| {mean:.3g}, "
+                      f"{100.0 * eq / px:.2f} % bit-equal")
+                continue
             print(f"  image of {v}: {'bit-identical to' if np.array_equal(im, first) else 'DIFFERS from'} "
                   f"{a.variants[0]} ({int((im != first).any(axis=-1).sum())} pixels differ)")
     for d in scenes.values():

@@ -162,6 +162,211 @@ __device__ __forceinline__ f3 refract(f3 I, f3 N, float eta)
     return eta * I - N * (eta * d + sqrt_exact(k));
 }
 __device__ __forceinline__ float sign1(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
+
+/* ---- arithmetic modes (WCPT_OPTION_ARITH) ---------------------------------------------------------------------
+ * kArithExact is everything above and below as written: the reference's operand order, unfused, correctly rounded
+ * reciprocal and square root, software log / cos -- bit-identical to the oracle. kArithFast is the megakernel's render
+ * builds only (the A template parameter, a distinct kernel symbol per mode) and relaxes, piece by piece:
+ *   WCPT_FAST_FMA    dot and cross products of the triangle tests, reflect / refract / Fresnel sums, normalize and
+ *                    `p + t * d` as fused multiply-adds (the sphere test's stay unfused, see WCPT_FAST_FMA_SPHERE),
+ *                    written out (__builtin_fmaf, __builtin_elementwise_fma = v_pk_fma_f32). Every translation unit
+ *                    stays on -ffp-contract=off: which products fuse is defined here, once per formula, never chosen by
+ *                    the compiler per call site -- the uniform and the per-lane leaf loops, every instantiation and every
+ *                    tile order evaluate the same helper, so a pixel's bits do not depend on which pixels share its wave
+ *                    (fast against fast stays bit for bit across row splits, tile orders, stacks, pipes and groups).
+ *   WCPT_FAST_RCP    1/x and v / s as the bare v_rcp_f32 (1 ULP): no Newton step, class check or fallback branch.
+ *   WCPT_FAST_SQRT   sqrt as the bare v_sqrt_f32 (1 ULP).
+ *   WCPT_FAST_TRANS  RandomValueNormalDistribution's log as v_log_f32 x ln 2 and its cos(2 pi u) as v_cos_f32(u) (the
+ *                    instruction takes revolutions: the 2 pi multiply and the range reduction both go).
+ * Each switch set to 0 keeps that piece exact in the fast kernels, so an A/B can price it (tools/ab_build.sh).
+ * (WCPT_FAST_RCP=0 does not build with ROCm 7.2: hipcc's register allocator crashes on one fast instantiation.)
+ * Unchanged in both modes: the PCG stream, every integer decision (take_bits, the minimum3 acceptance, the sign
+ * pre-reject), the traversal order, the slab test's (plane - origin) * inv form, wcpt_expf, the primary ray, the frame
+ * accumulation, store_pixel / display_rgba8 and the derived records as the runtime builds them. */
+constexpr int kArithExact = 0, kArithFast = 1;
+#ifndef WCPT_FAST_FMA
+#define WCPT_FAST_FMA 1
+#endif
+#ifndef WCPT_FAST_RCP
+#define WCPT_FAST_RCP 1
+#endif
+#ifndef WCPT_FAST_SQRT
+#define WCPT_FAST_SQRT 1
+#endif
+#ifndef WCPT_FAST_TRANS
+#define WCPT_FAST_TRANS 1
+#endif
+/* Where the fused forms apply, site by site: the triangle tests and the shading arithmetic (default: WCPT_FAST_FMA) and
+ * the sphere test (default 0). A site switched off evaluates the fast mode's other pieces on the exact mode's unfused
+ * formulas (kArithFastUnfused, internal: never a kernel's A).
+ * The sphere test stays unfused because its near root -b - sqrt(b * b - c), c = dot(oc, oc) - r * r, is dominated by
+ * cancellation on a large sphere: on the reference scene's ground sphere (r = 100) dot(oc, oc) and b * b are ~1e4 (one
+ * ULP ~1e-3) and c ~1e2, so rounding one product less moves t by ~1e-5 relative -- a hundred times the ULP-level
+ * differences of every other relaxation, and more than the kBias offset of the next origin -- without being any more
+ * accurate. Measured (MI355X, diverged pixels against the oracle, sphere products fused / unfused): the reference's scene
+ * 52x44 x 6 frames 20 / 6 of 2288, 128x96 34 / 8 of 12288, 256x192 133 / 54 of 49152; default_dielectric 128x96 28 / 8;
+ * the Cornell box 128x96 14 / 9. With the triangle or the shading products unfused instead, the reference's scene stays
+ * at 20 / 17 of 2288. Four sphere tests per segment are a small share of the VALU work. */
+#ifndef WCPT_FAST_FMA_TRI
+#define WCPT_FAST_FMA_TRI WCPT_FAST_FMA
+#endif
+#ifndef WCPT_FAST_FMA_SPHERE
+#define WCPT_FAST_FMA_SPHERE 0
+#endif
+#ifndef WCPT_FAST_FMA_SHADE
+#define WCPT_FAST_FMA_SHADE WCPT_FAST_FMA
+#endif
+constexpr int kArithFastUnfused = 2;
+template <int A> constexpr bool kFuse = A == kArithFast;
+template <int A> constexpr int kTriA = (A == kArithFast && !(WCPT_FAST_FMA_TRI)) ? kArithFastUnfused : A;
+template <int A> constexpr int kSphereA = (A == kArithFast && !(WCPT_FAST_FMA_SPHERE)) ? kArithFastUnfused : A;
+template <int A> constexpr int kShadeA = (A == kArithFast && !(WCPT_FAST_FMA_SHADE)) ? kArithFastUnfused : A;
+__device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
+template <int A>
+__device__ __forceinline__ float rcp_a(float x)
+{
+    if constexpr (A != kArithExact && WCPT_FAST_RCP) return __builtin_amdgcn_rcpf(x);
+    else return rcp_exact(x);
+}
+template <int A>
+__device__ __forceinline__ v2f rcp2_a(v2f x)
+{
+    if constexpr (A != kArithExact && WCPT_FAST_RCP) {
+        v2f r;
+        r.x = __builtin_amdgcn_rcpf(x.x);
+        r.y = __builtin_amdgcn_rcpf(x.y);
+        return r;
+    } else {
+        return rcp2_exact(x);
+    }
+}
+template <int A>
+__device__ __forceinline__ f3 rcp3_a(f3 a) { return mk3(rcp_a<A>(a.x), rcp_a<A>(a.y), rcp_a<A>(a.z)); }
+template <int A>
+__device__ __forceinline__ float sqrt_a(float x)
+{
+    if constexpr (A != kArithExact && WCPT_FAST_SQRT) return __builtin_amdgcn_sqrtf(x);
+    else return sqrt_exact(x);
+}
+/* a / b of two scalars: the IEEE quotient, or a * rcp(b) */
+template <int A>
+__device__ __forceinline__ float div_a(float a, float b)
+{
+    if constexpr (A != kArithExact && WCPT_FAST_RCP) return a * __builtin_amdgcn_rcpf(b);
+    else return a / b;
+}
+template <int A>
+__device__ __forceinline__ f3 div3_a(f3 a, float s)
+{
+    const float r = rcp_a<A>(s);
+    return mk3(a.x * r, a.y * r, a.z * r);
+}
+/* a * b + c and a * b - c * d as one formula per mode */
+template <int A>
+__device__ __forceinline__ float mad_a(float a, float b, float c)
+{
+    if constexpr (kFuse<A>) return __builtin_fmaf(a, b, c);
+    else return a * b + c;
+}
+template <int A>
+__device__ __forceinline__ float msub_a(float a, float b, float c, float d) /* a * b - c * d */
+{
+    if constexpr (kFuse<A>) return __builtin_fmaf(a, b, -(c * d));
+    else return a * b - c * d;
+}
+template <int A>
+__device__ __forceinline__ float nmad_a(float c, float a, float b) /* c - a * b */
+{
+    if constexpr (kFuse<A>) return __builtin_fmaf(-a, b, c);
+    else return c - a * b;
+}
+template <int A>
+__device__ __forceinline__ float madn_a(float a, float b, float c) /* a * b - c */
+{
+    if constexpr (kFuse<A>) return __builtin_fmaf(a, b, -c);
+    else return a * b - c;
+}
+template <int A>
+__device__ __forceinline__ v2f nmad2_a(v2f c, v2f a, v2f b)
+{
+    if constexpr (kFuse<A>) return fma2(-a, b, c);
+    else return c - a * b;
+}
+template <int A>
+__device__ __forceinline__ v2f madn2_a(v2f a, v2f b, v2f c)
+{
+    if constexpr (kFuse<A>) return fma2(a, b, -c);
+    else return a * b - c;
+}
+template <int A>
+__device__ __forceinline__ v2f mad2_a(v2f a, v2f b, v2f c)
+{
+    if constexpr (kFuse<A>) return fma2(a, b, c);
+    else return a * b + c;
+}
+template <int A>
+__device__ __forceinline__ v2f msub2_a(v2f a, v2f b, v2f c, v2f d)
+{
+    if constexpr (kFuse<A>) return fma2(a, b, -(c * d));
+    else return a * b - c * d;
+}
+/* (x * x' + y * y') + z * z'; fused: fma(z, z', fma(y, y', x * x')) */
+template <int A>
+__device__ __forceinline__ float dot_a(f3 a, f3 b)
+{
+    if constexpr (kFuse<A>) return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x));
+    else return dot(a, b);
+}
+template <int A>
+__device__ __forceinline__ v2f dot2_a(v2f ax, v2f ay, v2f az, v2f bx, v2f by, v2f bz)
+{
+    if constexpr (kFuse<A>) return fma2(az, bz, fma2(ay, by, ax * bx));
+    else return (ax * bx + ay * by) + az * bz;
+}
+template <int A>
+__device__ __forceinline__ f3 cross_a(f3 a, f3 b)
+{
+    if constexpr (kFuse<A>)
+        return mk3(msub_a<A>(a.y, b.z, b.y, a.z), msub_a<A>(a.z, b.x, b.z, a.x), msub_a<A>(a.x, b.y, b.x, a.y));
+    else return cross(a, b);
+}
+/* a + b * s per component (p + t * d, base + roughness * rd, p + n * bias) */
+template <int A>
+__device__ __forceinline__ f3 axpy_a(f3 a, f3 b, float s)
+{
+    if constexpr (kFuse<A>)
+        return mk3(__builtin_fmaf(b.x, s, a.x), __builtin_fmaf(b.y, s, a.y), __builtin_fmaf(b.z, s, a.z));
+    else return a + b * s;
+}
+template <int A>
+__device__ __forceinline__ f3 normalize_a(f3 v)
+{
+    if constexpr (A != kArithExact) return div3_a<A>(v, sqrt_a<A>(dot_a<A>(v, v)));
+    else return normalize(v);
+}
+template <int A>
+__device__ __forceinline__ f3 reflect_a(f3 I, f3 N)
+{
+    if constexpr (kFuse<A>) {
+        const float k = -2.0f * dot_a<A>(N, I);
+        return axpy_a<A>(I, N, k);
+    } else {
+        return reflect(I, N);
+    }
+}
+template <int A>
+__device__ __forceinline__ f3 refract_a(f3 I, f3 N, float eta)
+{
+    if constexpr (A != kArithExact) {
+        const float d = dot_a<A>(N, I);
+        const float k = nmad_a<A>(1.0f, eta * eta, nmad_a<A>(1.0f, d, d)); /* 1 - eta^2 (1 - d^2) */
+        if (k < 0.0f) return mk3(0.0f, 0.0f, 0.0f);
+        const float c = -mad_a<A>(eta, d, sqrt_a<A>(k));
+        return axpy_a<A>(eta * I, N, c);
+    } else {
+        return refract(I, N, eta);
+    }
+}
 __device__ __forceinline__ f3 ld3(const float* p) { return mk3(p[0], p[1], p[2]); }
 __device__ __forceinline__ f3 ld3(gf32_ptr p) { return mk3(p[0], p[1], p[2]); } /* global_load_dwordx3 */
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -263,8 +468,32 @@ __device__ __forceinline__ v2f cosf_2pi2(v2f ax)
     out.y = cos_quadrant(j1, c.y, sn.y);
     return out;
 }
+/* The fast mode's normal variate (Random.glsl:32-41): ln(u) = log2(u) * ln 2 on v_log_f32, so rho = sqrt(log2(u) *
+ * (-2 ln 2)), and cos(2 pi u) = v_cos_f32(u), whose operand is in revolutions. u = 0 gives rho = +inf as in the exact
+ * mode (log(0) = -inf). Same draws from the PCG stream, in the same order. */
+__device__ __forceinline__ float log_fast(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994530942f; }
+__device__ __forceinline__ float cos2pi_fast(float u) { return __builtin_amdgcn_cosf(u); }
+__device__ __forceinline__ float normal_fast(uint32_t& seed)
+{
+    const float u0 = rand_f(seed);
+    const float u1 = rand_f(seed);
+    const float rho = sqrt_a<kArithFast>(-2.0f * log_fast(u1));
+    return rho * cos2pi_fast(u0);
+}
+template <int A = kArithExact>
 __device__ __forceinline__ f3 RandomDirection(uint32_t& seed)
 {
+    if constexpr (A != kArithExact && WCPT_FAST_TRANS) {
+        const float x = normal_fast(seed);
+        const float y = normal_fast(seed);
+        const float z = normal_fast(seed);
+        return normalize_a<A>(mk3(x, y, z));
+    } else if constexpr (A != kArithExact) {
+        const float x = RandomValueNormalDistribution(seed);
+        const float y = RandomValueNormalDistribution(seed);
+        const float z = RandomValueNormalDistribution(seed);
+        return normalize_a<A>(mk3(x, y, z));
+    } else {
 #if WCPT_RANDDIR_PAIRS
     /* Random.glsl:43-56 with the draws in the reference order: theta_x, rho_x, theta_y, rho_y, theta_z, rho_z */
     const float ux0 = rand_f(seed), ux1 = rand_f(seed);
@@ -282,6 +511,7 @@ __device__ __forceinline__ f3 RandomDirection(uint32_t& seed)
     const float z = RandomValueNormalDistribution(seed);
     return normalize(mk3(x, y, z));
 #endif
+    }
 }
 
 /* ---- pathTracer.comp:24-28, 50-58 ------------------------------------------------------------- */
@@ -365,14 +595,16 @@ __device__ __forceinline__ void node_box(const Ray& r, const NodeV& n, float& t0
 }
 
 /* pathTracer.comp:110-119, near root only (:141) */
+template <int A = kArithExact>
 __device__ __forceinline__ float raySphereNear(const Ray& r, f3 position, float radius)
 {
+    constexpr int S = kSphereA<A>;
     const f3 oc = r.origin - position;
-    const float b = dot(oc, r.direction);
-    const float c = dot(oc, oc) - radius * radius;
-    const float t = b * b - c;
+    const float b = dot_a<S>(oc, r.direction);
+    const float c = nmad_a<S>(dot_a<S>(oc, oc), radius, radius); /* dot(oc, oc) - radius * radius */
+    const float t = madn_a<S>(b, b, c);                          /* b * b - c */
     if (t < 0.0f) return -1.0f;
-    return -b - sqrt_exact(t);
+    return -b - sqrt_a<S>(t);
 }
 
 /* The sphere loop of Intersect (pathTracer.comp:140-149) over spheres [0, count): the near root of each, accepted
@@ -386,9 +618,11 @@ constexpr uint32_t kNoPrim = 0xFFFFFFFFu, kSpherePrim = 0x80000000u;
 #ifndef WCPT_SPHERE_BSKIP
 #define WCPT_SPHERE_BSKIP 1
 #endif
+template <int A = kArithExact>
 __device__ __forceinline__ void sphere_loop(const Ray& r, uint32_t count, const wcpt_sphere* __restrict__ spheres,
                                             float& rt, uint32_t& prim)
 {
+    constexpr int S = kSphereA<A>;
     uint32_t i = 0;
 #if WCPT_SPHERE_PAIRS
     const v2f ox = {r.origin.x, r.origin.x}, oy = {r.origin.y, r.origin.y}, oz = {r.origin.z, r.origin.z};
@@ -400,17 +634,17 @@ __device__ __forceinline__ void sphere_loop(const Ray& r, uint32_t count, const 
         const v2f cx = {s0.position[0], s1.position[0]}, cy = {s0.position[1], s1.position[1]},
                     cz = {s0.position[2], s1.position[2]}, rad = {s0.radius, s1.radius};
         const v2f ocx = ox - cx, ocy = oy - cy, ocz = oz - cz;     /* oc = origin - position */
-        const v2f b = (ocx * dx + ocy * dy) + ocz * dz;           /* dot(oc, d) */
-        const v2f c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - rad * rad;
-        const v2f t = b * b - c;
+        const v2f b = dot2_a<S>(ocx, ocy, ocz, dx, dy, dz);        /* dot(oc, d) */
+        const v2f c = nmad2_a<S>(dot2_a<S>(ocx, ocy, ocz, ocx, ocy, ocz), rad, rad); /* dot(oc, oc) - rad * rad */
+        const v2f t = madn2_a<S>(b, b, c);                         /* b * b - c */
 #if WCPT_SPHERE_BSKIP
         /* b >= 0 (the centre is not ahead of the origin) gives -b - sqrt(t) <= 0 exactly, so RN of it is <= 0 and the
          * `t0 > 0` test below fails either way: the square root is skipped (NaN b still takes the full path) */
-        const float t0 = (t.x < 0.0f || b.x >= 0.0f) ? -1.0f : -b.x - sqrt_exact(t.x);
-        const float t1 = (t.y < 0.0f || b.y >= 0.0f) ? -1.0f : -b.y - sqrt_exact(t.y);
+        const float t0 = (t.x < 0.0f || b.x >= 0.0f) ? -1.0f : -b.x - sqrt_a<S>(t.x);
+        const float t1 = (t.y < 0.0f || b.y >= 0.0f) ? -1.0f : -b.y - sqrt_a<S>(t.y);
 #else
-        const float t0 = t.x < 0.0f ? -1.0f : -b.x - sqrt_exact(t.x);
-        const float t1 = t.y < 0.0f ? -1.0f : -b.y - sqrt_exact(t.y);
+        const float t0 = t.x < 0.0f ? -1.0f : -b.x - sqrt_a<S>(t.x);
+        const float t1 = t.y < 0.0f ? -1.0f : -b.y - sqrt_a<S>(t.y);
 #endif
         if (t0 > 0.0f && t0 < rt) { rt = t0; prim = kSpherePrim | i; }
         if (t1 > 0.0f && t1 < rt) { rt = t1; prim = kSpherePrim | (i + 1u); }
@@ -418,7 +652,7 @@ __device__ __forceinline__ void sphere_loop(const Ray& r, uint32_t count, const 
 #endif
     for (; i < count; i++) {
         const wcpt_sphere& s = spheres[i];
-        const float tempRec = raySphereNear(r, mk3(s.position[0], s.position[1], s.position[2]), s.radius);
+        const float tempRec = raySphereNear<A>(r, mk3(s.position[0], s.position[1], s.position[2]), s.radius);
         if (tempRec > 0.0f && tempRec < rt) {
             rt = tempRec;
             prim = kSpherePrim | i;
@@ -474,15 +708,17 @@ __device__ __forceinline__ uint32_t take_bits(float t) { return __float_as_uint(
 __device__ __forceinline__ bool accept_uvw(float u, float v, float w) { return minimum3(u, v, w) >= 0.0f; }
 
 /* pathTracer.comp:121-133 with the two edges given: e1 = b - a, e2 = c - a (:122-123); returns t or -1 */
+template <int A = kArithExact>
 __device__ __forceinline__ float rayTriangleE(const Ray& r, f3 a, f3 edgeAB, f3 edgeAC)
 {
+    constexpr int TA = kTriA<A>;
     const f3 oa = r.origin - a;
-    const f3 crossRDE2 = cross(r.direction, edgeAC);
-    const float inv = rcp_exact(dot(edgeAB, crossRDE2));
-    const f3 crossROAE1 = cross(oa, edgeAB);
-    const float u = dot(oa, crossRDE2) * inv;
-    const float v = dot(r.direction, crossROAE1 * inv);
-    const float t = dot(edgeAC, crossROAE1) * inv;
+    const f3 crossRDE2 = cross_a<TA>(r.direction, edgeAC);
+    const float inv = rcp_a<TA>(dot_a<TA>(edgeAB, crossRDE2));
+    const f3 crossROAE1 = cross_a<TA>(oa, edgeAB);
+    const float u = dot_a<TA>(oa, crossRDE2) * inv;
+    const float v = dot_a<TA>(r.direction, crossROAE1 * inv);
+    const float t = dot_a<TA>(edgeAC, crossROAE1) * inv;
     return accept_tri(t, u, v, u + v) ? t : -1.0f;
 }
 __device__ __forceinline__ float rayTriangle(const Ray& r, f3 a, f3 b, f3 c) { return rayTriangleE(r, a, b - a, c - a); }
@@ -591,29 +827,31 @@ struct PairHit { v2f t; bool hit0, hit1; };
 #ifndef WCPT_PAIR_PIN
 #define WCPT_PAIR_PIN 1
 #endif
+template <int A = kArithExact>
 __device__ __forceinline__ PairHit rayTrianglePair(const Ray& r, const TriPair& p)
 {
+    constexpr int TA = kTriA<A>;
     const v2f dx = bc2(r.direction.x), dy = bc2(r.direction.y), dz = bc2(r.direction.z);
     const v2f oax = bc2(r.origin.x) - p.ax, oay = bc2(r.origin.y) - p.ay, oaz = bc2(r.origin.z) - p.az;
     /* crossRDE2 = cross(d, e2) */
-    const v2f px = dy * p.e2z - p.e2y * dz;
-    const v2f py = dz * p.e2x - p.e2z * dx;
-    const v2f pz = dx * p.e2y - p.e2x * dy;
-    const v2f det = (p.e1x * px + p.e1y * py) + p.e1z * pz;
+    const v2f px = msub2_a<TA>(dy, p.e2z, p.e2y, dz);
+    const v2f py = msub2_a<TA>(dz, p.e2x, p.e2z, dx);
+    const v2f pz = msub2_a<TA>(dx, p.e2y, p.e2x, dy);
+    const v2f det = dot2_a<TA>(p.e1x, p.e1y, p.e1z, px, py, pz);
     /* crossROAE1 = cross(oa, e1) */
-    const v2f qx = oay * p.e1z - p.e1y * oaz;
-    const v2f qy = oaz * p.e1x - p.e1z * oax;
-    const v2f qz = oax * p.e1y - p.e1x * oay;
-    const v2f un = (oax * px + oay * py) + oaz * pz; /* dot(oa, crossRDE2) */
-    const v2f tn = (p.e2x * qx + p.e2y * qy) + p.e2z * qz; /* dot(edgeAC, crossROAE1) */
+    const v2f qx = msub2_a<TA>(oay, p.e1z, p.e1y, oaz);
+    const v2f qy = msub2_a<TA>(oaz, p.e1x, p.e1z, oax);
+    const v2f qz = msub2_a<TA>(oax, p.e1y, p.e1x, oay);
+    const v2f un = dot2_a<TA>(oax, oay, oaz, px, py, pz);          /* dot(oa, crossRDE2) */
+    const v2f tn = dot2_a<TA>(p.e2x, p.e2y, p.e2z, qx, qy, qz);    /* dot(edgeAC, crossROAE1) */
 #if WCPT_PAIR_PIN
     /* computed before the reciprocal: its fallback branch would otherwise split the block, and these independent
      * products would be sunk past it instead of filling the det -> rcp -> Newton chain's dependency stalls */
     asm volatile("" ::"v"(qx), "v"(qy), "v"(qz), "v"(un), "v"(tn));
 #endif
-    const v2f inv = rcp2_exact(det);
+    const v2f inv = rcp2_a<TA>(det);
     const v2f u = un * inv;
-    const v2f v = (dx * (qx * inv) + dy * (qy * inv)) + dz * (qz * inv);
+    const v2f v = dot2_a<TA>(dx, dy, dz, qx * inv, qy * inv, qz * inv);
     const v2f t = tn * inv;
     const v2f uv = u + v;
     PairHit h;
@@ -669,16 +907,18 @@ __device__ __forceinline__ TriPairP load_pairP_const(const WCPT_GLOBAL char* bas
     return unpack_pairP((ctri_ptr)(uintptr_t)(base + off));
 }
 /* rayTrianglePair with the origin terms taken from the record: the remaining operations are rayTrianglePair's */
+template <int A = kArithExact>
 __device__ __forceinline__ PairHit rayTrianglePairP(const Ray& r, const TriPairP& p)
 {
+    constexpr int TA = kTriA<A>;
     const v2f dx = bc2(r.direction.x), dy = bc2(r.direction.y), dz = bc2(r.direction.z);
-    const v2f px = dy * p.e2z - p.e2y * dz;
-    const v2f py = dz * p.e2x - p.e2z * dx;
-    const v2f pz = dx * p.e2y - p.e2x * dy;
-    const v2f det = (p.e1x * px + p.e1y * py) + p.e1z * pz;
-    const v2f inv = rcp2_exact(det);
-    const v2f u = ((p.oax * px + p.oay * py) + p.oaz * pz) * inv;
-    const v2f v = (dx * (p.qx * inv) + dy * (p.qy * inv)) + dz * (p.qz * inv);
+    const v2f px = msub2_a<TA>(dy, p.e2z, p.e2y, dz);
+    const v2f py = msub2_a<TA>(dz, p.e2x, p.e2z, dx);
+    const v2f pz = msub2_a<TA>(dx, p.e2y, p.e2x, dy);
+    const v2f det = dot2_a<TA>(p.e1x, p.e1y, p.e1z, px, py, pz);
+    const v2f inv = rcp2_a<TA>(det);
+    const v2f u = dot2_a<TA>(p.oax, p.oay, p.oaz, px, py, pz) * inv;
+    const v2f v = dot2_a<TA>(dx, dy, dz, p.qx * inv, p.qy * inv, p.qz * inv);
     const v2f t = p.tq * inv;
     const v2f uv = u + v;
     PairHit h;
@@ -708,28 +948,35 @@ __device__ __forceinline__ PairHit rayTrianglePairP(const Ray& r, const TriPairP
  * so every result is the reference's. On primary rays (all from the camera, directions within one 8x8 tile) the sign
  * of det -- which side of the triangle's plane the ray heads to -- is nearly uniform across a wave: on Cornell ~21 %
  * of the primary pair steps are skippable by the whole wave (tools/prereject_sim.py; under 3 % on bounce rays, whose
- * directions are random per lane, where the test therefore is not made). */
+ * directions are random per lane, where the test therefore is not made).
+ * The argument needs only sign(rcp(det)) = sign(det) and rcp(+-0) = +-inf. Both hold for the bare v_rcp_f32 of the fast
+ * arithmetic mode as for the corrected reciprocal (the instruction keeps the operand's sign, and a denormal det it may
+ * flush is a zero of the same sign), so the fast kernels skip the same way: there t = RN(tq * rcp(det)). */
 #ifndef WCPT_PRIM_SIGN_SKIP
 #define WCPT_PRIM_SIGN_SKIP 1
 #endif
 #ifndef WCPT_PAIR_PREFETCH
 #define WCPT_PAIR_PREFETCH 0
 #endif
+template <int A = kArithExact>
 __device__ __forceinline__ v2f pairP_det(const Ray& r, const TriPairP& p, v2f& px, v2f& py, v2f& pz)
 {
+    constexpr int TA = kTriA<A>;
     const v2f dx = bc2(r.direction.x), dy = bc2(r.direction.y), dz = bc2(r.direction.z);
-    px = dy * p.e2z - p.e2y * dz;
-    py = dz * p.e2x - p.e2z * dx;
-    pz = dx * p.e2y - p.e2x * dy;
-    return (p.e1x * px + p.e1y * py) + p.e1z * pz;
+    px = msub2_a<TA>(dy, p.e2z, p.e2y, dz);
+    py = msub2_a<TA>(dz, p.e2x, p.e2z, dx);
+    pz = msub2_a<TA>(dx, p.e2y, p.e2x, dy);
+    return dot2_a<TA>(p.e1x, p.e1y, p.e1z, px, py, pz);
 }
 /* the rest of rayTrianglePairP after det (the same operations in the same order) */
+template <int A = kArithExact>
 __device__ __forceinline__ PairHit pairP_finish(const Ray& r, const TriPairP& p, v2f px, v2f py, v2f pz, v2f det)
 {
+    constexpr int TA = kTriA<A>;
     const v2f dx = bc2(r.direction.x), dy = bc2(r.direction.y), dz = bc2(r.direction.z);
-    const v2f inv = rcp2_exact(det);
-    const v2f u = ((p.oax * px + p.oay * py) + p.oaz * pz) * inv;
-    const v2f v = (dx * (p.qx * inv) + dy * (p.qy * inv)) + dz * (p.qz * inv);
+    const v2f inv = rcp2_a<TA>(det);
+    const v2f u = dot2_a<TA>(p.oax, p.oay, p.oaz, px, py, pz) * inv;
+    const v2f v = dot2_a<TA>(dx, dy, dz, p.qx * inv, p.qy * inv, p.qz * inv);
     const v2f t = p.tq * inv;
     const v2f uv = u + v;
     PairHit h;
@@ -1117,6 +1364,7 @@ struct LdsStack {
 /* Geometric normal of the triangle at index positions prim..prim+2 of draw `draw` (:173): from its single record
  * when the triangle starts on a triangle boundary inside the records (the record was derived from exactly these
  * three indices), else recomputed from the index and vertex buffers with the same expression. */
+template <int A = kArithExact>
 __device__ __forceinline__ f3 triangle_normal(uint32_t prim, uint32_t draw, const wcpt_draw_command* __restrict__ draws,
                                               const uint64_t* __restrict__ tri_records)
 {
@@ -1128,11 +1376,12 @@ __device__ __forceinline__ f3 triangle_normal(uint32_t prim, uint32_t draw, cons
     }
     const TriE e = tri_from_indices(as_u32(draws[draw].indexBuffer), as_f32(draws[draw].vertexBuffer), prim,
                                     tri_records ? draw_vertex_count(tri_records, draw) : 0xFFFFFFFFu);
-    return normalize(cross(e.e1, e.e2));
+    return normalize_a<A>(cross_a<A>(e.e1, e.e2));
 }
 
 /* Intersect epilogue (:204-208) for winner `prim` (kNoPrim, kSpherePrim | sphere, or the index position of
  * a triangle of draw `draw`) at distance t. */
+template <int A = kArithExact>
 __device__ __forceinline__ Hit resolve_hit(const Ray& ray, float t, uint32_t prim, uint32_t draw,
                                            const wcpt_sphere* __restrict__ spheres,
                                            const wcpt_draw_command* __restrict__ draws,
@@ -1148,16 +1397,16 @@ __device__ __forceinline__ Hit resolve_hit(const Ray& ray, float t, uint32_t pri
         if (prim & kSpherePrim) {
             const wcpt_sphere& s = spheres[prim & ~kSpherePrim];
             const f3 c = mk3(s.position[0], s.position[1], s.position[2]);
-            const f3 ph = ray.origin + t * ray.direction;
-            h.normal = (ph - c) / s.radius;                        /* :145 */
+            const f3 ph = axpy_a<A>(ray.origin, ray.direction, t);
+            h.normal = div3_a<A>(ph - c, s.radius);                /* :145 */
             h.material = s.material;
         } else {
-            h.normal = triangle_normal(prim, draw, draws, tri_records); /* :173, material 0 (:175) */
+            h.normal = triangle_normal<A>(prim, draw, draws, tri_records); /* :173, material 0 (:175) */
         }
-        h.front = dot(ray.direction, h.normal) < 0.0f;
+        h.front = dot_a<A>(ray.direction, h.normal) < 0.0f;
         if (!h.front) h.normal = h.normal * -1.0f;
     }
-    h.p = ray.origin + t * ray.direction;                             /* :205 */
+    h.p = axpy_a<A>(ray.origin, ray.direction, t);                    /* :205 */
     return h;
 }
 
@@ -1235,15 +1484,15 @@ __device__ __forceinline__ void pair_take(const PairHit& ph, uint32_t off, float
     if (ph.hit1 && ph.t.y < rt) { rt = ph.t.y; tag = off + 1u; }
 #endif
 }
-template <bool COUNT, bool DIAG, bool UNIFORM, bool PRIM>
+template <bool COUNT, bool DIAG, bool UNIFORM, bool PRIM, int A = kArithExact>
 __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_t k0, uint32_t kend, float& rt,
                                           uint32_t& prim, Counters& cnt, PeelCache& pc)
 {
     constexpr uint32_t kBytes = PRIM ? kPrimPairRecordBytes : kPairRecordBytes;
     const WCPT_GLOBAL char* pbase = reinterpret_cast<const WCPT_GLOBAL char*>(recs);
     auto test_at = [&](uint32_t off) {
-        if constexpr (PRIM) return rayTrianglePairP(ray, load_pairP_at(pbase, off));
-        else return rayTrianglePair(ray, load_pair_at(pbase, off));
+        if constexpr (PRIM) return rayTrianglePairP<A>(ray, load_pairP_at(pbase, off));
+        else return rayTrianglePair<A>(ray, load_pair_at(pbase, off));
     };
     /* the peeled pair at `off`, through the per-segment cache */
     auto peeled_at = [&](uint32_t off) {
@@ -1309,7 +1558,7 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
                 TriPair cur = load_pair_const(pbase, offU);
                 for (uint32_t o = offU; o < endU; o += kBytes) {
                     const TriPair nxt = load_pair_const(pbase, o + kBytes);
-                    const PairHit ph = rayTrianglePair(ray, cur);
+                    const PairHit ph = rayTrianglePair<A>(ray, cur);
                     count_tri<COUNT, DIAG>(cnt);
                     count_tri<COUNT, DIAG>(cnt);
 #if WCPT_PAIR_ITAKE
@@ -1328,7 +1577,7 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
                 if constexpr (PRIM) {
                     const TriPairP p = load_pairP_const(pbase, o);
                     v2f px, py, pz;
-                    const v2f det = pairP_det(ray, p, px, py, pz);
+                    const v2f det = pairP_det<A>(ray, p, px, py, pz);
                     if (__builtin_amdgcn_ballot_w64(pairP_may_take(p, det)) == 0ull) {
                         /* no lane can take either triangle (t <= 0 or NaN for all): the reference's tests still
                          * ran (and are counted), and none would change rec.t */
@@ -1336,21 +1585,21 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
                         count_tri<COUNT, DIAG>(cnt);
                         continue;
                     }
-                    ph = pairP_finish(ray, p, px, py, pz, det);
+                    ph = pairP_finish<A>(ray, p, px, py, pz, det);
                 } else {
-                    ph = rayTrianglePair(ray, load_pair_const(pbase, o));
+                    ph = rayTrianglePair<A>(ray, load_pair_const(pbase, o));
                 }
 #else
-                if constexpr (PRIM) ph = rayTrianglePairP(ray, load_pairP_const(pbase, o));
-                else ph = rayTrianglePair(ray, load_pair_const(pbase, o));
+                if constexpr (PRIM) ph = rayTrianglePairP<A>(ray, load_pairP_const(pbase, o));
+                else ph = rayTrianglePair<A>(ray, load_pair_const(pbase, o));
 #endif
 #if WCPT_DUP_PAIR
                 {
                     Ray r2 = ray;
                     r2.direction.x = launder(r2.direction.x);
                     PairHit p2;
-                    if constexpr (PRIM) p2 = rayTrianglePairP(r2, load_pairP_const(pbase, o));
-                    else p2 = rayTrianglePair(r2, load_pair_const(pbase, o));
+                    if constexpr (PRIM) p2 = rayTrianglePairP<A>(r2, load_pairP_const(pbase, o));
+                    else p2 = rayTrianglePair<A>(r2, load_pair_const(pbase, o));
                     sink(p2.t.x + p2.t.y);
                     sink_u((p2.hit0 ? 1u : 0u) | (p2.hit1 ? 2u : 0u));
                 }
@@ -1373,7 +1622,7 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
         if constexpr (!PRIM) {
             Ray r2 = ray;
             r2.origin.x = launder(r2.origin.x);
-            const PairHit p2 = rayTrianglePair(r2, load_pair_at(pbase, off));
+            const PairHit p2 = rayTrianglePair<A>(r2, load_pair_at(pbase, off));
             sink(p2.t.x + p2.t.y);
             sink_u((p2.hit0 ? 1u : 0u) | (p2.hit1 ? 2u : 0u));
         }
@@ -1404,7 +1653,7 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
  * taken iff accepted with t < rec.t (strict). UNIFORM: the leaf's whole pairs may be read with scalar loads (the
  * draw's record base must then be wave-uniform). primary: the segment is a sample's first (origin = the camera,
  * wave-uniform), whose leaves are tested from the primary-ray pair records when the draw has them. */
-template <bool COUNT, bool DIAG, bool PAIRS, bool UNIFORM>
+template <bool COUNT, bool DIAG, bool PAIRS, bool UNIFORM, int A = kArithExact>
 __device__ __forceinline__ void leaf_step(const Ray& ray, const DrawGeom& g, uint32_t curLeft, uint32_t curCount,
                                           float& rt, uint32_t& prim, Counters& cnt, bool primary, PeelCache& pc)
 {
@@ -1413,16 +1662,16 @@ __device__ __forceinline__ void leaf_step(const Ray& ray, const DrawGeom& g, uin
         const uint32_t kend = k0 + (curCount + 2u) / 3u;
 #if WCPT_PRIMARY_PAIRS
         if (primary && g.ptris != nullptr)
-            pair_leaf<COUNT, DIAG, UNIFORM, true>(ray, g.ptris, k0, kend, rt, prim, cnt, pc);
+            pair_leaf<COUNT, DIAG, UNIFORM, true, A>(ray, g.ptris, k0, kend, rt, prim, cnt, pc);
         else
 #endif
-            pair_leaf<COUNT, DIAG, UNIFORM, false>(ray, g.tris, k0, kend, rt, prim, cnt, pc);
+            pair_leaf<COUNT, DIAG, UNIFORM, false, A>(ray, g.tris, k0, kend, rt, prim, cnt, pc);
     } else {
         for (uint32_t k = 0, j = 0; k < curCount; k += 3, j++) {
             const uint32_t first = k + curLeft;
             const TriE tr = (!PAIRS && k0 != kNoRecord) ? load_tri(g.tris, k0 + j)
                                                         : tri_from_indices(g.indices, g.vertices, first, g.nvert);
-            const float t = rayTriangleE(ray, tr.a, tr.e1, tr.e2);
+            const float t = rayTriangleE<A>(ray, tr.a, tr.e1, tr.e2);
             count_tri<COUNT, DIAG>(cnt);
             if (t != -1.0f && t < rt) {
                 rt = t;
@@ -1558,7 +1807,7 @@ __device__ __forceinline__ uint32_t* prim_cache_lane(uint32_t* tile_records)
 {
     return tile_records + (threadIdx.x & 63u) * (SINGLE ? 2u : 3u);
 }
-template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, int PC = kPrimCacheNone>
+template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, int PC = kPrimCacheNone, int A = kArithExact>
 __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& sd, const wcpt_sphere* __restrict__ spheres,
                                          const wcpt_draw_command* __restrict__ draws,
                                          const uint64_t* __restrict__ tri_records, Stack& stk,
@@ -1578,7 +1827,7 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
             simd_step<DIAG>(cnt.wave_seg, cnt.lane_seg);
         }
 
-        sphere_loop(ray, sd.sphereCount, spheres, rt, prim);
+        sphere_loop<A>(ray, sd.sphereCount, spheres, rt, prim);
         if (COUNT) cnt.sphere_tests += sd.sphereCount;
 #if WCPT_DUP_SPHERES
         {
@@ -1643,7 +1892,7 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
                     mode = interior_step<COUNT, DIAG>(ray, g, stk, curLeft, curCount, rt, cnt, overflow, rf)
                                ? (curCount > 0 ? kLeaf : kInterior) : kPop;
                 if (mode == kLeaf) {
-                    leaf_step<COUNT, DIAG, PAIRS, true>(ray, g, curLeft, curCount, rt, prim, cnt, primary, pc);
+                    leaf_step<COUNT, DIAG, PAIRS, true, A>(ray, g, curLeft, curCount, rt, prim, cnt, primary, pc);
                     mode = kPop;
                 }
             }
@@ -1667,7 +1916,7 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
             bool active = start_draw();
             while (active) {
                 if (curCount > 0) {
-                    leaf_step<COUNT, DIAG, PAIRS, false>(ray, g, curLeft, curCount, rt, prim, cnt, primary, pc);
+                    leaf_step<COUNT, DIAG, PAIRS, false, A>(ray, g, curLeft, curCount, rt, prim, cnt, primary, pc);
                 } else if (interior_step<COUNT, DIAG>(ray, g, stk, curLeft, curCount, rt, cnt, overflow, rf)) {
                     continue;
                 }
@@ -1687,25 +1936,26 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
     }
     if (COUNT && prim != kNoPrim) cnt.hits++;
     ref_segment_end<COUNT>(cnt);
-    const Hit hit = resolve_hit(ray, rt, prim, primDraw, spheres, draws, tri_records);
+    const Hit hit = resolve_hit<kShadeA<A>>(ray, rt, prim, primDraw, spheres, draws, tri_records);
     phase_mark(cnt, 4);
     return hit;
 }
 
 /* pathTracer.comp:213-234 */
+template <int A = kArithExact>
 __device__ __forceinline__ float CalculateReflectance(f3 inDir, f3 normal, float iorA, float iorB)
 {
-    const float refractRatio = iorA / iorB;
-    const float cosAngleIn = -dot(inDir, normal);
-    const float sinSqr = refractRatio * refractRatio * (1.0f - cosAngleIn * cosAngleIn);
+    const float refractRatio = div_a<A>(iorA, iorB);
+    const float cosAngleIn = -dot_a<A>(inDir, normal);
+    const float sinSqr = refractRatio * refractRatio * nmad_a<A>(1.0f, cosAngleIn, cosAngleIn);
     if (sinSqr >= 1.0f) return 1.0f;
-    const float cosRefr = sqrt_exact(1.0f - sinSqr);
-    const float dPerp = iorA * cosAngleIn + iorB * cosRefr;
-    const float dPar = iorB * cosAngleIn + iorA * cosRefr;
+    const float cosRefr = sqrt_a<A>(1.0f - sinSqr);
+    const float dPerp = mad_a<A>(iorA, cosAngleIn, iorB * cosRefr);
+    const float dPar = mad_a<A>(iorB, cosAngleIn, iorA * cosRefr);
     if (fminf(dPerp, dPar) < 1e-8f) return 1.0f;
-    float rPerp = (iorA * cosAngleIn - iorB * cosRefr) / dPerp;
+    float rPerp = div_a<A>(msub_a<A>(iorA, cosAngleIn, iorB, cosRefr), dPerp);
     rPerp *= rPerp;
-    float rPar = (iorB * cosAngleIn - iorA * cosRefr) / dPar;
+    float rPar = div_a<A>(msub_a<A>(iorB, cosAngleIn, iorA, cosRefr), dPar);
     rPar *= rPar;
     return (rPerp + rPar) / 2.0f;
 }
@@ -1726,11 +1976,12 @@ struct PathState {
     uint32_t bounce; /* loop index i of :245 */
 };
 
+template <int A = kArithExact>
 __device__ __forceinline__ void path_begin(PathState& ps, f3 origin, f3 dir)
 {
     ps.ray.origin = origin;
     ps.ray.direction = dir;
-    ps.ray.invDirection = rcp3(dir);
+    ps.ray.invDirection = rcp3_a<A>(dir);
     ps.totalLight = mk3(0.0f, 0.0f, 0.0f);
     ps.transmittance = mk3(1.0f, 1.0f, 1.0f);
     ps.bounce = 0;
@@ -1751,6 +2002,7 @@ __device__ __forceinline__ void path_begin(PathState& ps, f3 origin, f3 dir)
 /* Shading after an Intersect (pathTracer.comp:248-280). Returns true when the path is finished, with its
  * radiance in L: on a miss (:248-249) or when the bounce loop is exhausted (:245, :283). lastSample: this is the
  * pixel's last sample (its RNG state is not read after the path). */
+template <int A = kArithExact>
 __device__ __forceinline__ bool path_shade(PathState& ps, const Hit& h, uint32_t& rng, const wcpt_scene_data& sd,
                                            const wcpt_material* __restrict__ mats, f3& L, bool lastSample)
 {
@@ -1781,40 +2033,40 @@ __device__ __forceinline__ bool path_shade(PathState& ps, const Hit& h, uint32_t
      * RandomDirection (6 rand, 3 log, 3 cos, 4 sqrt) once instead of once per branch. Every lane performs the
      * reference's operations in the reference's order. */
     const bool metal = mtype == WCPT_MATERIAL_METAL;
-    const f3 R = reflect(ray.direction, h.normal);
+    const f3 R = reflect_a<A>(ray.direction, h.normal);
     f3 base = R;
     bool followReflection = true;
     if (!metal) {
         const float ior = m.ior;
         const float etaI = h.front ? 1.0f : ior;
         const float etaT = h.front ? ior : 1.0f;
-        const float reflectProb = CalculateReflectance(ray.direction, h.normal, etaI, etaT);
-        const f3 T = refract(ray.direction, h.normal, etaI / etaT);
+        const float reflectProb = CalculateReflectance<A>(ray.direction, h.normal, etaI, etaT);
+        const f3 T = refract_a<A>(ray.direction, h.normal, div_a<A>(etaI, etaT));
         followReflection = (T.x == 0.0f && T.y == 0.0f && T.z == 0.0f);
         if (!followReflection) followReflection = (rand_f(rng) <= reflectProb); /* :273 short-circuit */
         if (!followReflection) base = T;
     }
-    const f3 rd = RandomDirection(rng);
+    const f3 rd = RandomDirection<A>(rng);
 #if WCPT_DUP_RANDDIR
     {
         uint32_t r2 = launder_u(rng);
-        const f3 d2 = RandomDirection(r2);
+        const f3 d2 = RandomDirection<A>(r2);
         sink(d2.x + d2.y + d2.z);
     }
 #endif
-    const f3 dir = normalize(base + roughness * rd);
+    const f3 dir = normalize_a<A>(axpy_a<A>(base, rd, roughness));
     if (metal) {
-        ray.origin = h.p + h.normal * kBias;                                  /* :257 */
+        ray.origin = axpy_a<A>(h.p, h.normal, kBias);                         /* :257 */
         ps.transmittance = ps.transmittance * ld3(m.albedo);                  /* :261 */
     } else {
         if (!followReflection && !h.front) {                                  /* :276-278 */
             const f3 e = ((ld3(m.absorption) * -1.0f) * m.absorptionStrength) * h.t;
             ps.transmittance = ps.transmittance * mk3(wcpt_expf(e.x), wcpt_expf(e.y), wcpt_expf(e.z));
         }
-        ray.origin = h.p + (kBias * h.normal) * sign1(dot(dir, h.normal));   /* :279 */
+        ray.origin = h.p + (kBias * h.normal) * sign1(dot_a<A>(dir, h.normal)); /* :279 */
     }
     ray.direction = dir;
-    ray.invDirection = rcp3(dir);
+    ray.invDirection = rcp3_a<A>(dir);
 #else
     if (mtype == WCPT_MATERIAL_METAL) {
         ray.origin = h.p + h.normal * kBias;
@@ -1853,7 +2105,8 @@ __device__ __forceinline__ bool path_shade(PathState& ps, const Hit& h, uint32_t
 /* pathTracer.comp:241-284. prim_rec: the primary segment's Intersect record (t, primitive, draw), written by the
  * first sample; reuse_primary: a later sample, whose primary segment reads it instead of tracing the same ray again
  * (intersect). */
-template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, bool REUSE = false, int PC = kPrimCacheNone>
+template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, bool REUSE = false, int PC = kPrimCacheNone,
+          int A = kArithExact>
 __device__ __forceinline__ f3 TraceRay(Ray ray, uint32_t& rng, const wcpt_scene_data& sd,
                                        const wcpt_material* __restrict__ mats, const wcpt_sphere* __restrict__ spheres,
                                        const wcpt_draw_command* __restrict__ draws,
@@ -1862,7 +2115,7 @@ __device__ __forceinline__ f3 TraceRay(Ray ray, uint32_t& rng, const wcpt_scene_
                                        bool reuse_primary, uint32_t* __restrict__ pcache = nullptr)
 {
     PathState ps;
-    path_begin(ps, ray.origin, ray.direction);
+    path_begin<A>(ps, ray.origin, ray.direction);
     f3 L;
     /* segment counter of this sample: uniform across the wave's lanes (all start a sample together), so `primary`
      * (segment 0: origin = the camera) is a wave-uniform branch condition */
@@ -1872,9 +2125,9 @@ __device__ __forceinline__ f3 TraceRay(Ray ray, uint32_t& rng, const wcpt_scene_
         const bool reuse = PC == kPrimCacheRead ? seg == 0u : REUSE && seg == 0u && reuse_primary;
         /* the sample-reuse build keeps the record in prim_rec anyway: its write is the caller's, after sample 0 */
         constexpr int PCI = (PC == kPrimCacheWrite && REUSE) ? kPrimCacheNone : PC;
-        const Hit h = intersect<COUNT, DIAG, PAIRS, SINGLE, Stack, PCI>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
+        const Hit h = intersect<COUNT, DIAG, PAIRS, SINGLE, Stack, PCI, A>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
                                                                       overflow, primary, prim_rec, reuse, pcache);
-        const bool done = path_shade(ps, h, rng, sd, mats, L, lastSample);
+        const bool done = path_shade<kShadeA<A>>(ps, h, rng, sd, mats, L, lastSample);
         phase_mark(cnt, 5);
         if (done) return L;
     }

@@ -36,6 +36,7 @@ struct LaunchArgs {
     bool wf_fast;                /* wavefront trace: draw 0 has packed stack refs, 24-bit record offsets, leaves of < 255
                                     index positions on derived records (kTriFlagSmallLeaves, kTriFlagLeafRecords) and a known
                                     node count (table flags 1|2|4|8, word 2 high half > 0) */
+    int arith = WCPT_ARITH_EXACT; /* megakernel render launches: WCPT_ARITH_FAST takes the fast instances (WCPT_OPTION_ARITH) */
     uint32_t mk_tile_order;      /* static megakernel: 0 XCD-banded, 1 scattered, 2 auto, 3-6 striped bands (WCPT_OPTION_MK_TILE_ORDER) */
     float4* image;
     float* wire;                 /* gather payload (wcpt_set_gather_output) or null */

@@ -66,7 +66,7 @@ __device__ __forceinline__ void tile_of_block(uint32_t tilesX, uint32_t tilesTot
 }
 
 /* Shade one pixel (pathTracer.comp:290-323) with the given traversal stack. */
-template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, bool REUSE, int PC, class Stack>
+template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A, class Stack>
 __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcpt_material* __restrict__ mats,
                                             const wcpt_sphere* __restrict__ spheres,
                                             const wcpt_draw_command* __restrict__ draws,
@@ -103,7 +103,7 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
         r.origin = origin;
         r.direction = dir;
         r.invDirection = rcp3(dir);
-        result = result + TraceRay<COUNT, DIAG, PAIRS, SINGLE, Stack, REUSE, PC>(r, seed, sd, mats, spheres, draws, tri_records, stk, cnt, overflow,
+        result = result + TraceRay<COUNT, DIAG, PAIRS, SINGLE, Stack, REUSE, PC, A>(r, seed, sd, mats, spheres, draws, tri_records, stk, cnt, overflow,
                                                        s + 1u == samples, prim_rec, s > 0u, pcache);
     }
     if (PC == kPrimCacheWrite && REUSE) { /* this build (samples > 1) holds sample 0's record in prim_rec (TraceRay) */
@@ -135,7 +135,9 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
 #ifndef WCPT_MK_WAVES
 #define WCPT_MK_WAVES 1
 #endif
-template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE, int PC>
+/* A: the arithmetic mode (pt_device.h kArithExact / kArithFast, WCPT_OPTION_ARITH). A template parameter, so the fast
+ * and the exact kernel of one configuration are two symbols; render builds only (launch_mega_render). */
+template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A>
 __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_scene_data sd, const wcpt_material* __restrict__ mats,
                                                     const wcpt_sphere* __restrict__ spheres,
                                                     const wcpt_draw_command* __restrict__ draws,
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_sc
             uint64_t mem[kPrivateStack];
             PrivateStack<kPrivateStack> stk;
             stk.mem = (priv_u64_ptr)mem;
-            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE, PC>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
+            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE, PC, A>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
                                             cnt, overflow, pcache);
         } else {
             __shared__ uint64_t s_stack[kLdsStack * 64];
@@ -172,7 +174,7 @@ __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_sc
             LdsStack<kLdsStack, kSpillStack> stk;
             stk.base = (lds_u64_ptr)(s_stack + (threadIdx.x & 63u));
             stk.spill = (priv_u64_ptr)spill;
-            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE, PC>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
+            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE, PC, A>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
                                             cnt, overflow, pcache);
         }
     }
@@ -397,6 +399,19 @@ __global__ __launch_bounds__(256) void pt_selftest(int fn, const uint32_t* __res
         out[3u * i + 2u] = __float_as_uint(d.z);
         break;
     }
+    /* the fast arithmetic mode's device functions (pt_device.h kArithFast), mirroring fn 2, 3, 5, 9 and 7 */
+    case 18: out[i] = __float_as_uint(log_fast(__uint_as_float(a))); break;
+    case 19: out[i] = __float_as_uint(cos2pi_fast(__uint_as_float(a))); break; /* cos(2 pi u) given u */
+    case 20: out[i] = __float_as_uint(sqrt_a<kArithFast>(__uint_as_float(a))); break;
+    case 21: out[i] = __float_as_uint(rcp_a<kArithFast>(__uint_as_float(a))); break;
+    case 22: { /* fast RandomDirection: 3 words per input */
+        uint32_t s = a;
+        const f3 d = RandomDirection<kArithFast>(s);
+        out[3u * i + 0u] = __float_as_uint(d.x);
+        out[3u * i + 1u] = __float_as_uint(d.y);
+        out[3u * i + 2u] = __float_as_uint(d.z);
+        break;
+    }
     default: break;
     }
 }
@@ -439,7 +454,9 @@ hipError_t launch_build_primary_pairs(const void* pairs, uint32_t npairs, float 
  * below */
 static_assert(dev::kPrimCacheNone == kPrimaryCacheNone && dev::kPrimCacheWrite == kPrimaryCacheWrite &&
                   dev::kPrimCacheRead == kPrimaryCacheRead, "primary-cache modes");
-template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE = false, int PC = kPrimaryCacheNone>
+static_assert(dev::kArithExact == WCPT_ARITH_EXACT && dev::kArithFast == WCPT_ARITH_FAST, "arithmetic modes");
+template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE = false, int PC = kPrimaryCacheNone,
+          int A = WCPT_ARITH_EXACT>
 static hipError_t launch_mega(const LaunchArgs& a, MkState& mk, hipStream_t stream, uint32_t tilesX, uint32_t tiles,
                               const uint32_t* list, uint32_t grid)
 {
@@ -462,7 +479,8 @@ static hipError_t launch_mega(const LaunchArgs& a, MkState& mk, hipStream_t stre
      * a sort (launch_megakernel) take the tiles longest first */
     const bool cost_order = !COUNT && a.mk_tile_order == 2 && mk.cost != nullptr;
     const uint32_t* order = list ? list : (cost_order && mk.order_valid ? mk.order : nullptr);
-    hipLaunchKernelGGL((dev::pt_megakernel<COUNT, DIAG, SK, PAIRS, SINGLE, REUSE, PC>), dim3(list ? grid : tiles), dim3(64), 0,
+    static_assert(!COUNT || A == WCPT_ARITH_EXACT, "the counting builds are exact");
+    hipLaunchKernelGGL((dev::pt_megakernel<COUNT, DIAG, SK, PAIRS, SINGLE, REUSE, PC, A>), dim3(list ? grid : tiles), dim3(64), 0,
                        stream, a.sd, a.materials, a.spheres, a.draws, a.tri_records, a.image, a.wire, a.wire_ch, a.W, a.H,
                        RowMap{a.y0, a.row_shift, a.row_gap}, a.wire_rows, a.rows, tilesX, tiles, scatter, order,
                        cost_order ? mk.cost : nullptr, a.status, a.counters,
@@ -572,21 +590,32 @@ static hipError_t cost_order_sort(MkState& mk, uint32_t tiles, hipStream_t strea
     return e;
 }
 
-/* the render instantiations: sample reuse (samples > 1) x primary-cache mode of this render */
-template <int SK, bool PAIRS, bool SINGLE>
-static hipError_t launch_mega_render(const LaunchArgs& a, int pcmode, MkState& mk, hipStream_t stream, uint32_t tilesX,
+/* the render instantiations: sample reuse (samples > 1) x primary-cache mode of this render, in arithmetic mode A */
+template <int SK, bool PAIRS, bool SINGLE, int A>
+static hipError_t launch_mega_arith(const LaunchArgs& a, int pcmode, MkState& mk, hipStream_t stream, uint32_t tilesX,
                                      uint32_t tiles, const uint32_t* list, uint32_t grid)
 {
     const bool reuse = a.sd.samples > 1u && WCPT_MK_PRIMARY_REUSE;
     if (pcmode == kPrimaryCacheRead) /* its one-sample form holds the sample count as a constant: only for samples == 1 */
         return a.sd.samples != 1u
-                   ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheRead>(a, mk, stream, tilesX, tiles, list, grid)
-                   : launch_mega<false, false, SK, PAIRS, SINGLE, false, kPrimaryCacheRead>(a, mk, stream, tilesX, tiles, list, grid);
+                   ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheRead, A>(a, mk, stream, tilesX, tiles, list, grid)
+                   : launch_mega<false, false, SK, PAIRS, SINGLE, false, kPrimaryCacheRead, A>(a, mk, stream, tilesX, tiles, list, grid);
     if (pcmode == kPrimaryCacheWrite)
-        return reuse ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheWrite>(a, mk, stream, tilesX, tiles, list, grid)
-                     : launch_mega<false, false, SK, PAIRS, SINGLE, false, kPrimaryCacheWrite>(a, mk, stream, tilesX, tiles, list, grid);
-    return reuse ? launch_mega<false, false, SK, PAIRS, SINGLE, true>(a, mk, stream, tilesX, tiles, list, grid)
-                 : launch_mega<false, false, SK, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
+        return reuse ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheWrite, A>(a, mk, stream, tilesX, tiles, list, grid)
+                     : launch_mega<false, false, SK, PAIRS, SINGLE, false, kPrimaryCacheWrite, A>(a, mk, stream, tilesX, tiles, list, grid);
+    return reuse ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheNone, A>(a, mk, stream, tilesX, tiles, list, grid)
+                 : launch_mega<false, false, SK, PAIRS, SINGLE, false, kPrimaryCacheNone, A>(a, mk, stream, tilesX, tiles, list, grid);
+}
+
+/* WCPT_OPTION_ARITH (LaunchArgs::arith): the fast twin of every render instantiation; the count and diagnostics builds
+ * have none (launch_mega_sk) */
+template <int SK, bool PAIRS, bool SINGLE>
+static hipError_t launch_mega_render(const LaunchArgs& a, int pcmode, MkState& mk, hipStream_t stream, uint32_t tilesX,
+                                     uint32_t tiles, const uint32_t* list, uint32_t grid)
+{
+    return a.arith == WCPT_ARITH_FAST
+               ? launch_mega_arith<SK, PAIRS, SINGLE, WCPT_ARITH_FAST>(a, pcmode, mk, stream, tilesX, tiles, list, grid)
+               : launch_mega_arith<SK, PAIRS, SINGLE, WCPT_ARITH_EXACT>(a, pcmode, mk, stream, tilesX, tiles, list, grid);
 }
 
 /* pcmode: the render's primary-cache mode (the COUNT / DIAG builds never read or write the cache: their counters are

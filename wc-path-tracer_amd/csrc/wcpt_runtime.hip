@@ -154,6 +154,8 @@ struct wcpt_context {
     uint64_t scratch_bytes = 0;
     int kernel = WCPT_KERNEL_MEGAKERNEL;
     int kernel_run = WCPT_KERNEL_MEGAKERNEL; /* the variant the current/last render runs (WCPT_KERNEL_AUTO resolved) */
+    int arith = WCPT_ARITH_EXACT;      /* WCPT_OPTION_ARITH: a permission for megakernel render launches */
+    int arith_run = WCPT_ARITH_EXACT;  /* the arithmetic the current/last render runs (wcpt_last_arith) */
     int stack_kind = 1;                /* WCPT_OPTION_STACK: 0 scratch, 1 LDS + spill (default; c2 -2%, 135-row blocks -8%) */
     int diagnostics = 0;               /* WCPT_OPTION_DIAGNOSTICS */
     int sort_rays = 0;                 /* WCPT_OPTION_SORT_RAYS (wavefront only; measured a net loss on c3) */
@@ -731,6 +733,10 @@ int render_common(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t mate
     rc = prepare_tri_records(ctx, *scene, draws, a);
     if (rc) return rc;
     if (ctx->prep_missed) overlap = 0;
+    /* WCPT_OPTION_ARITH: only the megakernel's render instances have fast twins; the wavefront kernels (also as
+     * WCPT_KERNEL_AUTO's choice), the counting and the diagnostics runs are exact */
+    a.arith = (mode == wcpt::kModeRender && ctx->kernel_run == WCPT_KERNEL_MEGAKERNEL) ? ctx->arith : WCPT_ARITH_EXACT;
+    ctx->arith_run = a.arith;
     /* the other kernel's pending frames (the same image) first */
     if (ctx->kernel_run != WCPT_KERNEL_MEGAKERNEL && ctx->mk.pending)
         HIP_TRY(ctx, wcpt::mk_join(ctx->mk, ctx->stream), "frame overlap join");
@@ -1039,6 +1045,14 @@ int wcpt_last_kernel(wcpt_context* ctx, int* variant)
     return WCPT_SUCCESS;
 }
 
+int wcpt_last_arith(wcpt_context* ctx, int* arith)
+{
+    if (!ctx) return set_error(nullptr, WCPT_ERROR_INVALID_HANDLE, "null context");
+    if (!arith) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "null arith");
+    *arith = ctx->arith_run;
+    return WCPT_SUCCESS;
+}
+
 int wcpt_set_option(wcpt_context* ctx, int option, int value)
 {
     if (!ctx) return set_error(nullptr, WCPT_ERROR_INVALID_HANDLE, "null context");
@@ -1083,6 +1097,12 @@ int wcpt_set_option(wcpt_context* ctx, int option, int value)
         if (value < 0 || value > 1) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "primary cache %d", value);
         ctx->prim_cache = value;
         ctx->generation++;
+        return WCPT_SUCCESS;
+    case WCPT_OPTION_ARITH:
+        if (value != WCPT_ARITH_EXACT && value != WCPT_ARITH_FAST)
+            return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "arithmetic mode %d", value);
+        ctx->arith = value;
+        ctx->generation++; /* the primary cache's key holds the generation: a record belongs to the arithmetic that found it */
         return WCPT_SUCCESS;
     case WCPT_OPTION_WF_STACK:
         if (value != 10 && value != 16 && value != 24)
@@ -1522,8 +1542,8 @@ int wcpt_selftest_device(wcpt_context* ctx, int fn, const uint32_t* in, const ui
     if (rc) return rc;
     if (!in || !out || ((fn == 6 || fn == 14 || fn == 16 || fn == 17) && !in2))
         return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "null selftest arrays");
-    if (fn < 0 || fn > 17) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "unknown selftest fn %d", fn);
-    const uint64_t outw = (fn == 1) ? 4ull * n : (fn == 7 ? 3ull * n : (uint64_t)n);
+    if (fn < 0 || fn > 22) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "unknown selftest fn %d", fn);
+    const uint64_t outw = (fn == 1) ? 4ull * n : ((fn == 7 || fn == 22) ? 3ull * n : (uint64_t)n);
     rc = ensure_scratch(ctx, (2ull * n + outw) * 4ull + 16);
     if (rc) return rc;
     uint32_t* d_in = ctx->d_scratch;

@@ -58,6 +58,9 @@ OPTION_WF_PERSIST = 13
 OPTION_GATHER_FRAME_ROWS = 14
 OPTION_FRAME_OVERLAP = 15
 OPTION_PRIMARY_CACHE = 16
+OPTION_ARITH = 17       # the one option that changes results (wcpt.h WCPT_OPTION_ARITH)
+ARITH_EXACT = 0
+ARITH_FAST = 1
 DEFAULT_WF_PIPES = 0  # wcpt_runtime.hip: by queue length (2 or 3)
 
 # gather payload formats (wcpt_set_gather_output, wcpt_group_set_output)
@@ -149,6 +152,7 @@ _PROTOTYPES = {
     "wcpt_build_id": (C.c_char_p, []),
     "wcpt_device_count": (_i, [C.POINTER(_i)]),
     "wcpt_last_kernel": (_i, [_p, C.POINTER(_i)]),
+    "wcpt_last_arith": (_i, [_p, C.POINTER(_i)]),
     "wcpt_device_pci_bus_id": (_i, [_i, C.c_char_p, _i]),
     "wcpt_create": (_i, [_i, C.POINTER(_p)]),
     "wcpt_destroy": (_i, [_p]),

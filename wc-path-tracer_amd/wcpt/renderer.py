@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (COUNTER_FIELDS, DRAW_COMMAND_DTYPE, GROUP_OPTION_ROW_STRIPE, GROUP_TRANSPORT_RCCL,
-                   GROUP_UNIQUE_ID_BYTES, OPTION_DIAGNOSTICS,
+                   GROUP_UNIQUE_ID_BYTES, ARITH_EXACT, OPTION_ARITH, OPTION_DIAGNOSTICS,
                    MATERIAL_DTYPE, SCENE_DATA_DTYPE, SPHERE_DTYPE, Camera, Counters, GroupInfo, WcptError, check, lib, ptr)
 from . import scene as _scene
 
@@ -63,6 +63,12 @@ class Context:
         """The variant the last render ran (WCPT_KERNEL_AUTO resolved per render)."""
         v = C.c_int()
         self._chk(lib.wcpt_last_kernel(self.h, C.byref(v)))
+        return v.value
+
+    def last_arith(self) -> int:
+        """The arithmetic the last render ran (ARITH_FAST only after a megakernel render with OPTION_ARITH set to it)."""
+        v = C.c_int()
+        self._chk(lib.wcpt_last_arith(self.h, C.byref(v)))
         return v.value
 
     def set_option(self, option: int, value: int):
@@ -191,7 +197,7 @@ class Context:
 
     def selftest(self, fn: int, x: np.ndarray, x2: np.ndarray | None = None) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.uint32)
-        per = {1: 4, 7: 3}.get(fn, 1)
+        per = {1: 4, 7: 3, 22: 3}.get(fn, 1)
         out = np.empty(x.size * per, np.uint32)
         x2p = None
         if x2 is not None:
@@ -332,7 +338,9 @@ class Group:
 class PathTracingRenderer:
     """Host mirror of ``PathTracingRenderer`` (src/PathTracingRenderer.jai:92-123) over the C-ABI."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, arith: int = ARITH_EXACT):
+        """arith: ARITH_EXACT (default, bit-identical to the oracle) or ARITH_FAST (WCPT_OPTION_ARITH: the megakernel's
+        fast-arithmetic instances, for display)."""
         self.renderSize = (0, 0)
         self.samples = 1                 # :119
         self.maxBounceCount = 3          # :120
@@ -342,6 +350,8 @@ class PathTracingRenderer:
         self.spheres = np.zeros(0, dtype=SPHERE_DTYPE)
         self.meshes = []
         self.ctx = Context(device)
+        if arith != ARITH_EXACT:
+            self.ctx.set_option(OPTION_ARITH, arith)
         self._mat_buf = self._sph_buf = self._draw_buf = None
         self._mesh_bufs = []
 
