@@ -592,6 +592,26 @@ void     wcpt_string_free(char* text);
  * 22 = RandomDirection (3 per input). Host arrays of 32-bit words. */
 int      wcpt_selftest_device(wcpt_context* ctx, int fn, const uint32_t* in, const uint32_t* in2,
                               uint32_t* out, uint32_t n);
+/* Evaluates the composite device functions of the render kernels, called as those kernels call them, on n items in the
+ * arithmetic mode `arith` (WCPT_ARITH_EXACT or WCPT_ARITH_FAST; anything else: WCPT_ERROR_INVALID_ARGUMENT). Item i
+ * reads in[i * in_words ..) and writes out[i * out_words ..); both counts must be the function's (below). Floats are
+ * passed as their bit patterns; vectors as x, y, z.
+ *   fn 0  rayTriangleE         in 15: origin, direction, a, b, c (edges formed as b - a, c - a)   out 1: t, or -1 for a miss
+ *   fn 1  rayTrianglePair      in 24: origin, direction, (a, e1, e2) of triangle 0, of triangle 1
+ *                              out 4: t of each (the raw quotient, also when not accepted), then 1 / 0 per triangle:
+ *                              u >= 0, v >= 0, u + v <= 1 (the take adds 0 < t < rec.t)
+ *   fn 2  rayTrianglePairP     as fn 1, on the primary-ray record that build_primary_pairs derives for this origin
+ *   fn 3  raySphereNear        in 10: origin, direction, centre, radius                           out 1: t, or -1
+ *   fn 4  resolve_hit, sphere  in 11: origin, direction, t, centre, radius                        out 7: p, normal, front
+ *   fn 5  reflect, refract (eta = iorA / iorB), CalculateReflectance
+ *                              in 8: direction, normal, iorA, iorB                                out 7: R, T, reflectProb
+ *   fn 6  normalize and the component reciprocals            in 3: v                              out 6: v / |v|, 1 / v
+ *   fn 7  one path_shade step (not the last segment, a hit)
+ *                              in 33: origin, direction, the Hit's p, normal, t, front (1 / 0), one wcpt_material
+ *                              (15 words), the rng state, transmittance
+ *                              out 10: the next origin, direction, transmittance, the rng state */
+int      wcpt_selftest_geometry(wcpt_context* ctx, int fn, int arith, const uint32_t* in, uint32_t in_words,
+                                uint32_t* out, uint32_t out_words, uint32_t n);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -28,7 +28,9 @@ import wcpt
 import oracle
 from wcpt import dist
 
-from test_gpu_parity import _variant, assert_close, get_scene
+from wcpt import scene as wscene
+
+from test_gpu_parity import _random_scene, _variant, _with_mesh, assert_close, get_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +44,7 @@ def _bits(img):
 
 
 def _scene(name):
-    if name == "two_draws":
+    if name in ("two_draws", "all_dielectric", "no_meshes", "empty"):
         return _variant("cornell", name)
     return get_scene(name)
 
@@ -349,9 +351,14 @@ def test_statistics_against_the_oracle(name, w, h, bounces, nframes, spp):
     order of STAT_CASES: 39 / 0.060 % / 3.5e-4 / 96.8 %; 9 / 0.073 % / 4.4e-4 / 88.3 %; 3 / 0.131 % / 2.0e-4 / 73.5 %;
     8 / 0.065 % / 6.7e-5 / 86.3 %; 8 / 0.065 % / 8.7e-5 / 88.0 %; 6 / 0.262 % / 7.1e-5 / 86.4 %; 3 / 0.131 % / 5.5e-4 /
     89.7 %; 3 / 0.131 % / 1.4e-4 / 72.4 %."""
-    img = _fast(name, bounces, nframes, spp, w, h)
-    ref = _oracle(name, bounces, nframes, spp, w, h)
+    _assert_statistics(_fast(name, bounces, nframes, spp, w, h), _oracle(name, bounces, nframes, spp, w, h),
+                       f"{name} {w}x{h} b{bounces} x{nframes} spp{spp}")
+
+
+def _assert_statistics(img, ref, what):
+    """(a) at most 0.5 % of the pixels diverge, (b) the median relative difference is <= 1e-6, (c) finiteness matches."""
     assert img.shape == ref.shape
+    h, w = img.shape[:2]
     a, b = img[..., :3].astype(np.float64), ref[..., :3].astype(np.float64)
     both = np.isfinite(a) & np.isfinite(b)
     d = np.abs(np.where(both, a, 0.0) - np.where(both, b, 0.0))
@@ -360,7 +367,7 @@ def test_statistics_against_the_oracle(name, w, h, bounces, nframes, spp):
     diverged = int((~close).any(axis=-1).sum())        # includes a finite / non-finite mismatch
     median = float(np.median(rel))
     equal = (_bits(img) == _bits(ref)).all(axis=-1).mean()
-    print(f"{name} {w}x{h} b{bounces} x{nframes} spp{spp}: diverged {diverged} / {w * h} "
+    print(f"{what}: diverged {diverged} / {w * h} "
           f"({100.0 * diverged / (w * h):.3f} %), median rel {median:.3g}, mean |d| {d.mean():.3g}, "
           f"bit-equal {100 * equal:.2f} %")
     assert diverged <= 0.005 * w * h, f"(a) {diverged} diverged pixels of {w * h}"
@@ -454,3 +461,184 @@ def test_fast_random_direction(gpu_ctx):
     print(f"fast RandomDirection: max | |d| - 1 | {length.max():.3g}, max distance to exact {dist_.max():.3g}")
     assert length.max() <= 1e-6
     assert dist_.max() <= 1e-3
+
+
+# ---- 7. the instantiations the frames above never reach -------------------------------------------------------------
+# About 40 fast instantiations exist (stack kind x pair records x single draw x sample reuse x primary-cache mode); the
+# Cornell box keeps the traversal stack at three entries and its leaves on pair records. The atrium's 27-level tree spills
+# the LDS stack and walks thin leaves on single records. AW x AH leaves partial tiles at the bottom edge.
+AW, AH = 96, 54
+
+
+# -- bit for bit, fast against fast (one helper per formula, so a pixel's bits do not depend on the
+# -- instantiation, the stack or the pixels that share its wave)
+@pytest.mark.parametrize("option,value", [(T.OPTION_STACK, 0), (T.OPTION_PACKED_REFS, 0), (T.OPTION_MK_TILE_ORDER, 0),
+                                          (T.OPTION_MK_TILE_ORDER, 1), (T.OPTION_MK_TILE_ORDER, 3)])
+def test_atrium_fast_against_fast(option, value):
+    img = _render("atrium", FAST, range(3), 4, w=AW, h=AH, options=[(option, value)])
+    _assert_same(img, _fast("atrium", 4, 3, 1, AW, AH), f"option {option} = {value} against the default")
+
+
+def test_atrium_row_range():
+    """y0 = 13 is no multiple of 8: other pixels share a wave, and other tiles a block's neighbourhood."""
+    r = _Run(_scene("atrium"), FAST, AW, AH)
+    try:
+        r.ctx.set_row_range(13, 25)
+        for f in range(3):
+            r.render(f)
+        img = r.image(25)
+    finally:
+        r.close()
+    _assert_same(img, _fast("atrium", 4, 3, 1, AW, AH)[13:38], "rows 13..37")
+
+
+# -- statistics against the oracle
+def _frames(s, sds, w, h, options=(), init=None, prepare=None, arith=FAST):
+    """The image after rendering the scene data `sds` in turn on one context (over `init`), and the oracle's."""
+    r = _Run(s, arith, w, h, options)
+    try:
+        if prepare:
+            prepare(r)
+        if init is not None:
+            r.ctx.image_upload(init)
+        for sd in sds:
+            r.ctx.render(sd, *r.dev.addresses())
+        img = r.image()
+        assert r.ctx.last_arith() == arith
+    finally:
+        r.close()
+    return img
+
+
+def _oracle_frames(s, sds, w, h, init=None):
+    acc = init
+    for sd in sds:
+        acc, _ = oracle.render_scene(s, w, h, sd=sd, image=acc, threads=8)
+    return acc
+
+
+def test_statistics_atrium():
+    _assert_statistics(_fast("atrium", 4, 3, 1, AW, AH), _oracle("atrium", 4, 3, 1, AW, AH), "atrium 96x54 b4 x3")
+
+
+@pytest.mark.parametrize("name,option,w,h", [("cornell", T.OPTION_PAIR_RECORDS, W, H), ("atrium", T.OPTION_PAIR_RECORDS, AW, AH),
+                                             ("cornell", T.OPTION_TRIANGLE_CACHE, W, H)])
+def test_statistics_without_pair_records_or_triangle_cache(name, option, w, h):
+    """Single records on both scenes (the fast rayTriangleE), and no derived records at all (the index path)."""
+    img = _render(name, FAST, range(3), 4, w=w, h=h, options=[(option, 0)])
+    _assert_statistics(img, _oracle(name, 4, 3, 1, w, h), f"{name} option {option} = 0")
+
+
+def test_statistics_leaf_not_on_triangle_boundary():
+    """test_gpu_parity.test_leaf_not_on_triangle_boundary's hand-made BVH: a leaf that starts at index position 1 and a draw
+    whose indexCount covers fewer triangles than the leaves reference take the index path (tri_from_indices)."""
+    rng = np.random.default_rng(7)
+    ntri = 40
+    pos = (rng.random((ntri * 3, 3), dtype=np.float32) * 2.0 - 1.0).astype(np.float32)
+    pos[:, 2] -= 3.0
+    idx = np.arange(ntri * 3 + 2, dtype=np.uint32) % (ntri * 3)
+    lo, hi = pos.min(axis=0), pos.max(axis=0)
+    nodes = np.zeros(3, dtype=T.NODE_DTYPE)
+    nodes[0] = (lo, hi, 1, 0)
+    nodes[1] = (lo, hi, 1, 60)
+    nodes[2] = (lo, hi, 63, 3 * ntri - 63)
+    s = _with_mesh(get_scene("default"), wscene.HostBVH(pos, idx, nodes))
+
+    def short_draw(r):
+        draws = np.zeros(1, dtype=T.DRAW_COMMAND_DTYPE)
+        b = r.dev.buffers
+        draws[0] = (r.ctx.buffer_address(b[2]), r.ctx.buffer_address(b[3]), r.ctx.buffer_address(b[4]), 30, 0)
+        r.ctx.buffer_upload(b[5], draws)
+
+    sds = [s.scene_data(AW, AH, max_bounce=2, frame=f) for f in range(2)]
+    img = _frames(s, sds, AW, AH, prepare=short_draw)
+    exact = _frames(s, sds, AW, AH, prepare=short_draw, arith=EXACT)
+    ref = _oracle_frames(s, sds, AW, AH)
+    assert_close(exact, ref, exact=True)                     # the same set-up in the exact mode is the oracle's frame
+    assert (_bits(img) != _bits(ref)).any()
+    _assert_statistics(img, ref, "leaf not on a triangle boundary")
+
+
+def test_statistics_all_dielectric():
+    """Refraction, Fresnel and absorption on every hit, 6 bounces, 2 samples (the sample-reuse build)."""
+    _assert_statistics(_fast("all_dielectric", 6, 1, 2), _oracle("all_dielectric", 6, 1, 2), "all_dielectric b6 spp2")
+
+
+def test_statistics_moved_camera():
+    """test_gpu_parity.test_primary_records_follow_the_camera's sequence: the camera moves, moves back, and the mesh is
+    uploaded again -- the primary records (whose origin terms the fast mode reads unfused) are rebuilt each time."""
+    import ctypes
+    s = get_scene("cornell")
+    cams = []
+    for dx in (0.0, 0.35, 0.0):
+        cam = wcpt.Camera()
+        ctypes.pointer(cam)[0] = s.camera
+        cam.position[0] += dx
+        cam.position[1] += dx * 0.5
+        cams.append(cam)
+    r = _Run(s, FAST, AW, AH, [(T.OPTION_PAIR_RECORDS, 1)])
+    try:
+        for f, cam in enumerate(cams + [cams[-1]]):
+            if f == 3:
+                r.ctx.buffer_upload(r.dev.buffers[2], np.ascontiguousarray(s.meshes[0].positions, dtype=np.float32))
+            sd = s.scene_data(AW, AH, max_bounce=3, samples=2, frame=0, camera=cam)
+            r.ctx.render(sd, *r.dev.addresses())
+            img = r.image()
+            assert r.ctx.last_arith() == FAST
+            ref, _ = oracle.render_scene(s, AW, AH, sd=sd, threads=8)
+            _assert_statistics(img, ref, f"camera {f}")
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2, 3])
+def test_statistics_random_scenes(seed):
+    s, bounces, spp, frame = _random_scene(seed)
+    init = np.random.default_rng(seed + 100).random((AH, AW, 4)).astype(np.float32)
+    sds = [s.scene_data(AW, AH, max_bounce=bounces, samples=spp, frame=frame)]
+    _assert_statistics(_frames(s, sds, AW, AH, init=init), _oracle_frames(s, sds, AW, AH, init=init),
+                       f"random scene {seed} b{bounces} spp{spp} frame {frame}")
+
+
+@pytest.mark.parametrize("frame", [1, 7, 1000])
+def test_statistics_progressive_accumulation(frame):
+    """One fast frame mixed into a random image with weight 1 / (frame + 1): the accumulation itself is exact arithmetic."""
+    s = _scene("cornell")
+    init = np.random.default_rng(31).random((H, W, 4)).astype(np.float32)
+    sds = [s.scene_data(W, H, max_bounce=4, frame=frame)]
+    _assert_statistics(_frames(s, sds, W, H, init=init), _oracle_frames(s, sds, W, H, init=init), f"frame {frame}")
+
+
+# -- edge inputs
+def test_samples_zero():
+    """The reference divides by zero samples (:312): NaN colour in both modes, the same alpha."""
+    s = _scene("cornell")
+    sds = [s.scene_data(W, H, max_bounce=3, samples=0)]
+    img, ref = _frames(s, sds, W, H), _oracle_frames(s, sds, W, H)
+    assert np.isnan(img[..., :3]).all() and np.isnan(ref[..., :3]).all()
+    assert np.array_equal(_bits(img)[..., 3], _bits(ref)[..., 3])
+
+
+@pytest.mark.parametrize("bounces", [0, 12])
+def test_statistics_bounce_counts(bounces):
+    _assert_statistics(_fast("cornell", bounces, 1), _oracle("cornell", bounces, 1), f"maxBounceCount {bounces}")
+
+
+def test_empty_scene_is_exact():
+    """Sky only. No relaxed operation reaches a sky pixel: the primary direction and ray_color are exact code in both modes,
+    the fast reciprocal of path_begin's invDirection is read by the traversal only, and with no sphere and no draw there
+    is none -- so the fast frame is the oracle's, bit for bit."""
+    assert_close(_fast("empty", 3, 2), _oracle("empty", 3, 2), exact=True)
+
+
+def test_statistics_no_meshes():
+    """Spheres only. The pixels that see a sphere go through the sphere test's v_sqrt_f32 (raySphereNear stays unfused but
+    takes the bare square root) and the fused shading arithmetic, so the frame gets the statistics; its sky pixels (those
+    the oracle never lets hit anything) must be the oracle's bits, as in the empty scene."""
+    img, ref = _fast("no_meshes", 3, 1), _oracle("no_meshes", 3, 1)
+    _assert_statistics(img, ref, "no_meshes")
+    sky = _oracle("empty", 3, 1)
+    is_sky = (_bits(ref) == _bits(sky)).all(axis=-1)
+    assert 0 < is_sky.sum() < W * H
+    same = (_bits(img) == _bits(ref)).all(axis=-1)
+    assert same[is_sky].mean() >= 0.995, "sky pixels differ"

@@ -223,6 +223,11 @@ void wf_release(WfState& s);
 void wf_release(WfPipes& w);
 hipError_t launch_selftest(int fn, const uint32_t* in, const uint32_t* in2, uint32_t* out, uint32_t n,
                            hipStream_t stream);
+/* wcpt_selftest_geometry: the words one item of `fn` reads and writes (false: no such fn), and the launch in arithmetic
+ * mode `arith` (WCPT_ARITH_*) over n items */
+bool selftest_geometry_words(int fn, uint32_t& in_words, uint32_t& out_words);
+hipError_t launch_selftest_geometry(int fn, int arith, const uint32_t* in, uint32_t in_words, uint32_t* out,
+                                    uint32_t out_words, uint32_t n, hipStream_t stream);
 
 /* wcpt_runtime.hip internals used by the multi-device group (wcpt_group.hip) */
 hipStream_t context_stream(wcpt_context* ctx);

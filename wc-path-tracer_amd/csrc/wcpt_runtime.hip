@@ -1557,4 +1557,30 @@ int wcpt_selftest_device(wcpt_context* ctx, int fn, const uint32_t* in, const ui
     return WCPT_SUCCESS;
 }
 
+int wcpt_selftest_geometry(wcpt_context* ctx, int fn, int arith, const uint32_t* in, uint32_t in_words, uint32_t* out,
+                           uint32_t out_words, uint32_t n)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (!in || !out) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "null selftest arrays");
+    if (arith != WCPT_ARITH_EXACT && arith != WCPT_ARITH_FAST)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "unknown arithmetic mode %d", arith);
+    uint32_t iw = 0, ow = 0;
+    if (!wcpt::selftest_geometry_words(fn, iw, ow))
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "unknown geometry selftest fn %d", fn);
+    if (in_words != iw || out_words != ow)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "geometry selftest fn %d takes %u words and gives %u per item", fn,
+                         iw, ow);
+    const uint64_t inw = (uint64_t)n * iw, outw = (uint64_t)n * ow;
+    rc = ensure_scratch(ctx, (inw + outw) * 4ull + 16);
+    if (rc) return rc;
+    uint32_t* d_in = ctx->d_scratch;
+    uint32_t* d_out = d_in + inw;
+    HIP_TRY(ctx, hipMemcpyAsync(d_in, in, 4ull * inw, hipMemcpyHostToDevice, ctx->stream), "selftest upload");
+    HIP_TRY(ctx, wcpt::launch_selftest_geometry(fn, arith, d_in, iw, d_out, ow, n, ctx->stream), "selftest launch");
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, 4ull * outw, hipMemcpyDeviceToHost, ctx->stream), "selftest download");
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    return WCPT_SUCCESS;
+}
+
 } /* extern "C" */

@@ -194,6 +194,7 @@ _PROTOTYPES = {
     "wcpt_mesh_to_obj": (_i, [C.POINTER(Mesh), C.POINTER(C.c_void_p), C.POINTER(_u64)]),
     "wcpt_string_free": (None, [C.c_void_p]),
     "wcpt_selftest_device": (_i, [_p, _i, _p, _p, _p, _u32]),
+    "wcpt_selftest_geometry": (_i, [_p, _i, _i, _p, _u32, _p, _u32, _u32]),
     "wcpt_runtime_version": (_i, [C.POINTER(_i)]),
     "wcpt_row_block": (_i, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "wcpt_row_stripes": (_i, [_u32, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),

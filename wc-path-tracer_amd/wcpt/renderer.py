@@ -206,6 +206,18 @@ class Context:
         self._chk(lib.wcpt_selftest_device(self.h, fn, ptr(x), x2p, ptr(out), x.size))
         return out
 
+    GEOMETRY_WORDS = {0: (15, 1), 1: (24, 4), 2: (24, 4), 3: (10, 1), 4: (11, 7), 5: (8, 7), 6: (3, 6), 7: (33, 10)}
+
+    def selftest_geometry(self, fn: int, arith: int, x: np.ndarray, out_words: int | None = None) -> np.ndarray:
+        """wcpt_selftest_geometry on the items x[n, in_words] (32-bit words): the output words, [n, out_words]."""
+        x = np.ascontiguousarray(x, dtype=np.uint32)
+        assert x.ndim == 2
+        if out_words is None:
+            out_words = self.GEOMETRY_WORDS[fn][1]
+        out = np.empty((x.shape[0], out_words), np.uint32)
+        self._chk(lib.wcpt_selftest_geometry(self.h, fn, arith, ptr(x), x.shape[1], ptr(out), out_words, x.shape[0]))
+        return out
+
 
 class DeviceScene:
     """A HostScene resident in device buffers: the six DBufferManagers of PathTracingRenderer.jai:110-117."""
