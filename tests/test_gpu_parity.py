@@ -167,7 +167,7 @@ def test_device_acceptance_forms_agree(gpu_ctx):
 
 
 def test_device_integer_take_exhaustive(gpu_ctx):
-    """The integer form of the triangle take (pt_device.h take_bits, WCPT_PAIR_ITAKE): for rec.t any positive float the
+    """The integer form of the triangle take (pt_device.h take_bits): for rec.t any positive float the
     kernel can hold (kInfinity, the largest floats, ordinary distances, the smallest normal and denormal values, +inf),
     `t > 0 && t < rec.t` equals `bits(t) - 1 < bits(rec.t) - 1` on ALL 2^32 t (zeros, denormals, negatives, NaNs)."""
     rts = np.array([3.402823466e38, 3.4028233e38, np.inf, 1.0, 0.5, 2.0, 1e-3, 7.25, 123456.0, 1.1754944e-38,
@@ -662,8 +662,8 @@ def test_edge_inputs_match_oracle(gpu_ctx, kernel, kind, bounces, spp):
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("bounces,spp", [(0, 1), (2, 2), (4, 1), (3, 3)])
 def test_last_segment_shortcuts_match_oracle(gpu_ctx, kernel, bounces, spp):
-    """The last segment of a pixel's last sample ends after its emission term (WCPT_LAST_SEGMENT_SHORTCUT) and the
-    wavefront traces it as any-hit (WCPT_WF_ANYHIT_LAST): exact only because every triangle carries material 0
+    """The last segment of a pixel's last sample ends after its emission term (path_shade's shortcut) and the
+    wavefront traces it as any-hit (wf_trace's `any`): exact only because every triangle carries material 0
     (:175). Material 0 is made emissive here, so the triangle answer of that segment reaches the image, and
     samples > 1 checks that only the last sample takes the shortcut (its RNG state feeds the next sample)."""
     import copy

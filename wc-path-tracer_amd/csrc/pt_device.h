@@ -61,10 +61,7 @@ __device__ __forceinline__ f3 operator*(float s, f3 a) { return mk3(s * a.x, s *
  * quotient is flushed) or NaN (x zero, denormal, infinite or NaN), never a normal number. So the fast result is
  * validated on its own class (one v_cmp_class): a normal result is the IEEE quotient, anything else takes the
  * general division. Checked over all 2^32 inputs: selftest fn 12 (0 mismatches), which also runs the packed pair
- * form rcp2_exact. WCPT_RCP_RANGE=1 selects the older input-range test (two compares). */
-#ifndef WCPT_RCP_RANGE
-#define WCPT_RCP_RANGE 0
-#endif
+ * form rcp2_exact. */
 __device__ __forceinline__ float rcp_fast_raw(float x)
 {
     const float y = __builtin_amdgcn_rcpf(x);
@@ -74,27 +71,15 @@ __device__ __forceinline__ float rcp_fast_raw(float x)
 __device__ __forceinline__ bool rcp_fast_ok(float r) { return __builtin_isnormal(r); }
 __device__ __forceinline__ float rcp_exact(float x)
 {
-#if WCPT_RCP_RANGE
-    const float a = fabsf(x);
-    if (__builtin_expect(a >= 0x1p-126f && a < 0x1p126f, 1)) return rcp_fast_raw(x);
-    return 1.0f / x;
-#else
     const float r = rcp_fast_raw(x);
     if (__builtin_expect(rcp_fast_ok(r), 1)) return r;
     return 1.0f / x;
-#endif
 }
 typedef float v2f __attribute__((ext_vector_type(2)));
 /* rcp_exact of both halves: two v_rcp_f32, the Newton step as two packed FMAs (v_pk_fma_f32: two independent
  * binary32 fused multiply-adds, the same operations as the scalar step) and one branch for both fallbacks. */
 __device__ __forceinline__ v2f rcp2_exact(v2f x)
 {
-#if WCPT_RCP_RANGE
-    v2f r;
-    r.x = rcp_exact(x.x);
-    r.y = rcp_exact(x.y);
-    return r;
-#else
     v2f y;
     y.x = __builtin_amdgcn_rcpf(x.x);
     y.y = __builtin_amdgcn_rcpf(x.y);
@@ -107,7 +92,6 @@ __device__ __forceinline__ v2f rcp2_exact(v2f x)
         if (!oky) r.y = 1.0f / x.y;
     }
     return r;
-#endif
 }
 __device__ __forceinline__ f3 rcp3(f3 a) { return mk3(rcp_exact(a.x), rcp_exact(a.y), rcp_exact(a.z)); }
 /* GLSL vector / scalar (normalize, the sphere normal :145, target.xyz / target.w :301, result / samples :312):
@@ -130,10 +114,7 @@ __device__ __forceinline__ f3 cross(f3 a, f3 b)
  * FMA residuals, wrapped in a 2^32 scaling for inputs below 2^-96 and a zero/infinity class fixup: 17 VALU. For
  * x >= 2^-96 (including +inf) the correction alone is the IEEE square root -- checked against sqrtf over every such
  * input on the device (selftest fn 15) -- so that range takes the 9-VALU core and everything else (tiny, zero,
- * negative, NaN) the full sequence. WCPT_SQRT_CORE=0 uses sqrtf everywhere. */
-#ifndef WCPT_SQRT_CORE
-#define WCPT_SQRT_CORE 1
-#endif
+ * negative, NaN) the full sequence. */
 __device__ __forceinline__ float sqrt_core(float x)
 {
     const float s = __builtin_amdgcn_sqrtf(x);
@@ -147,9 +128,7 @@ __device__ __forceinline__ float sqrt_core(float x)
 }
 __device__ __forceinline__ float sqrt_exact(float x)
 {
-#if WCPT_SQRT_CORE
     if (__builtin_expect(x >= 0x1p-96f, 1)) return sqrt_core(x);
-#endif
     return sqrtf(x);
 }
 __device__ __forceinline__ f3 normalize(f3 v) { return v / sqrt_exact(dot(v, v)); }
@@ -404,9 +383,6 @@ __device__ __forceinline__ float RandomValueNormalDistribution(uint32_t& seed)
  * order per half, with the float arithmetic on packed FP32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32
  * for the reciprocal's Newton step) and the integer and rounding steps per half. Bit-identical to the scalar
  * functions (and so to the oracle) by construction; selftest fn 7 checks RandomDirection against the oracle. */
-#ifndef WCPT_RANDDIR_PAIRS
-#define WCPT_RANDDIR_PAIRS 1
-#endif
 __device__ __forceinline__ v2f bcast2(float s) { v2f r = {s, s}; return r; }
 __device__ __forceinline__ v2f logf_rand2(v2f x)
 {
@@ -494,7 +470,6 @@ __device__ __forceinline__ f3 RandomDirection(uint32_t& seed)
         const float z = RandomValueNormalDistribution(seed);
         return normalize_a<A>(mk3(x, y, z));
     } else {
-#if WCPT_RANDDIR_PAIRS
     /* Random.glsl:43-56 with the draws in the reference order: theta_x, rho_x, theta_y, rho_y, theta_z, rho_z */
     const float ux0 = rand_f(seed), ux1 = rand_f(seed);
     const float uy0 = rand_f(seed), uy1 = rand_f(seed);
@@ -505,12 +480,6 @@ __device__ __forceinline__ f3 RandomDirection(uint32_t& seed)
     const v2f xy = rho * cosf_2pi2(theta);
     const float z = RandomValueNormalDistribution(seed);
     return normalize(mk3(xy.x, xy.y, z));
-#else
-    const float x = RandomValueNormalDistribution(seed);
-    const float y = RandomValueNormalDistribution(seed);
-    const float z = RandomValueNormalDistribution(seed);
-    return normalize(mk3(x, y, z));
-#endif
     }
 }
 
@@ -608,23 +577,16 @@ __device__ __forceinline__ float raySphereNear(const Ray& r, f3 position, float 
 }
 
 /* The sphere loop of Intersect (pathTracer.comp:140-149) over spheres [0, count): the near root of each, accepted
- * iff 0 < t < rec.t, in sphere order. WCPT_SPHERE_PAIRS=1 (default) evaluates two spheres per step with packed
+ * iff 0 < t < rec.t, in sphere order. Two spheres are evaluated per step with packed
  * FP32 (v_pk_mul_f32 / v_pk_add_f32: per half exactly raySphereNear's binary32 operations), the square roots and
  * the ordered takes per sphere. */
 constexpr uint32_t kNoPrim = 0xFFFFFFFFu, kSpherePrim = 0x80000000u;
-#ifndef WCPT_SPHERE_PAIRS
-#define WCPT_SPHERE_PAIRS 1
-#endif
-#ifndef WCPT_SPHERE_BSKIP
-#define WCPT_SPHERE_BSKIP 1
-#endif
 template <int A = kArithExact>
 __device__ __forceinline__ void sphere_loop(const Ray& r, uint32_t count, const wcpt_sphere* __restrict__ spheres,
                                             float& rt, uint32_t& prim)
 {
     constexpr int S = kSphereA<A>;
     uint32_t i = 0;
-#if WCPT_SPHERE_PAIRS
     const v2f ox = {r.origin.x, r.origin.x}, oy = {r.origin.y, r.origin.y}, oz = {r.origin.z, r.origin.z};
     const v2f dx = {r.direction.x, r.direction.x}, dy = {r.direction.y, r.direction.y},
                 dz = {r.direction.z, r.direction.z};
@@ -637,19 +599,13 @@ __device__ __forceinline__ void sphere_loop(const Ray& r, uint32_t count, const 
         const v2f b = dot2_a<S>(ocx, ocy, ocz, dx, dy, dz);        /* dot(oc, d) */
         const v2f c = nmad2_a<S>(dot2_a<S>(ocx, ocy, ocz, ocx, ocy, ocz), rad, rad); /* dot(oc, oc) - rad * rad */
         const v2f t = madn2_a<S>(b, b, c);                         /* b * b - c */
-#if WCPT_SPHERE_BSKIP
         /* b >= 0 (the centre is not ahead of the origin) gives -b - sqrt(t) <= 0 exactly, so RN of it is <= 0 and the
          * `t0 > 0` test below fails either way: the square root is skipped (NaN b still takes the full path) */
         const float t0 = (t.x < 0.0f || b.x >= 0.0f) ? -1.0f : -b.x - sqrt_a<S>(t.x);
         const float t1 = (t.y < 0.0f || b.y >= 0.0f) ? -1.0f : -b.y - sqrt_a<S>(t.y);
-#else
-        const float t0 = t.x < 0.0f ? -1.0f : -b.x - sqrt_a<S>(t.x);
-        const float t1 = t.y < 0.0f ? -1.0f : -b.y - sqrt_a<S>(t.y);
-#endif
         if (t0 > 0.0f && t0 < rt) { rt = t0; prim = kSpherePrim | i; }
         if (t1 > 0.0f && t1 < rt) { rt = t1; prim = kSpherePrim | (i + 1u); }
     }
-#endif
     for (; i < count; i++) {
         const wcpt_sphere& s = spheres[i];
         const float tempRec = raySphereNear<A>(r, mk3(s.position[0], s.position[1], s.position[2]), s.radius);
@@ -677,9 +633,6 @@ __device__ __forceinline__ bool accept_tri(float t, float u, float v, float uv)
  * >= 0; uv > 1 means uv >= 1 + 2^-23, so 1 - uv <= -2^-23 rounds to a negative number; uv = -inf gives +inf and
  * passes as `uv <= 1` does. The device self-test fn 14 compares both forms on special and random operands. The
  * pair test forms w for both triangles with one packed subtraction: 4.5 VALU per triangle instead of 5. */
-#ifndef WCPT_ACCEPT_MIN3
-#define WCPT_ACCEPT_MIN3 1
-#endif
 __device__ __forceinline__ float minimum3(float a, float b, float c)
 {
     return __builtin_elementwise_minimum(__builtin_elementwise_minimum(a, b), c);
@@ -689,7 +642,7 @@ __device__ __forceinline__ bool accept_tri_w(float t, float u, float v, float w)
     return t > 0.0f && minimum3(u, v, w) >= 0.0f;
 }
 
-/* Integer form of the take (WCPT_PAIR_ITAKE). The reference takes an accepted triangle iff t > 0 (:132) and t < rec.t
+/* Integer form of the take (take_bits). The reference takes an accepted triangle iff t > 0 (:132) and t < rec.t
  * (:171). For rec.t a positive float (kInfinity at most, or an earlier accepted t > 0; never NaN), the two compares
  * are one unsigned compare of bit patterns minus one: bits(t) - 1 < bits(rec.t) - 1. Positive floats (denormals
  * included: IEEE compares them as nonzero) order like their bit patterns; t = +0 gives 0 - 1 = 0xFFFFFFFF, which is
@@ -701,9 +654,6 @@ __device__ __forceinline__ bool accept_tri_w(float t, float u, float v, float w)
  * rec.t values (tests/test_gpu_parity.py). Measured (round 5, 6 interleaved rounds on two boxes,
  * profiles/r05_itake_ab.log): c2 kernel 0.3635 against 0.3651 ms (-0.4 %), the reference's scene +0.3 %; the same
  * form confined to the uniform loop gained less on c2 (-0.15 %). */
-#ifndef WCPT_PAIR_ITAKE
-#define WCPT_PAIR_ITAKE 1
-#endif
 __device__ __forceinline__ uint32_t take_bits(float t) { return __float_as_uint(t) - 1u; }
 __device__ __forceinline__ bool accept_uvw(float u, float v, float w) { return minimum3(u, v, w) >= 0.0f; }
 
@@ -784,12 +734,6 @@ __device__ __forceinline__ TriPair load_pair(gtri_ptr t, uint32_t j)
 /* The pair record at byte offset `off` from the record base (pair j at off = 80 j). */
 constexpr uint32_t kPairRecordBytes = 16u * kPairRecordFloat4s;
 constexpr uint32_t kNoTag = 0xFFFFFFFFu;
-#ifndef WCPT_PAIR_UNIFORM
-#define WCPT_PAIR_UNIFORM 1
-#endif
-#ifndef WCPT_PAIR_SLOOP
-#define WCPT_PAIR_SLOOP 1
-#endif
 
 __device__ __forceinline__ TriPair load_pair_at(const WCPT_GLOBAL char* base, uint32_t off)
 {
@@ -824,9 +768,6 @@ __device__ __forceinline__ v2f bc2(float s) { v2f r = {s, s}; return r; }
  * the reference's acceptance test (t > 0, u, v, u + v in range). A triangle is taken iff it passed and t < rec.t;
  * that equals the reference's `t != -1 && t < rec.t` on its -1-for-miss result (a pass implies t > 0). */
 struct PairHit { v2f t; bool hit0, hit1; };
-#ifndef WCPT_PAIR_PIN
-#define WCPT_PAIR_PIN 1
-#endif
 template <int A = kArithExact>
 __device__ __forceinline__ PairHit rayTrianglePair(const Ray& r, const TriPair& p)
 {
@@ -844,11 +785,9 @@ __device__ __forceinline__ PairHit rayTrianglePair(const Ray& r, const TriPair& 
     const v2f qz = msub2_a<TA>(oax, p.e1y, p.e1x, oay);
     const v2f un = dot2_a<TA>(oax, oay, oaz, px, py, pz);          /* dot(oa, crossRDE2) */
     const v2f tn = dot2_a<TA>(p.e2x, p.e2y, p.e2z, qx, qy, qz);    /* dot(edgeAC, crossROAE1) */
-#if WCPT_PAIR_PIN
     /* computed before the reciprocal: its fallback branch would otherwise split the block, and these independent
      * products would be sunk past it instead of filling the det -> rcp -> Newton chain's dependency stalls */
     asm volatile("" ::"v"(qx), "v"(qy), "v"(qz), "v"(un), "v"(tn));
-#endif
     const v2f inv = rcp2_a<TA>(det);
     const v2f u = un * inv;
     const v2f v = dot2_a<TA>(dx, dy, dz, qx * inv, qy * inv, qz * inv);
@@ -856,19 +795,10 @@ __device__ __forceinline__ PairHit rayTrianglePair(const Ray& r, const TriPair& 
     const v2f uv = u + v;
     PairHit h;
     h.t = t;
-#if WCPT_PAIR_ITAKE
     /* t > 0 is part of the take's integer compare (take_bits) */
     const v2f w = bc2(1.0f) - uv;
     h.hit0 = accept_uvw(u.x, v.x, w.x);
     h.hit1 = accept_uvw(u.y, v.y, w.y);
-#elif WCPT_ACCEPT_MIN3
-    const v2f w = bc2(1.0f) - uv;
-    h.hit0 = accept_tri_w(t.x, u.x, v.x, w.x);
-    h.hit1 = accept_tri_w(t.y, u.y, v.y, w.y);
-#else
-    h.hit0 = accept_tri(t.x, u.x, v.x, uv.x);
-    h.hit1 = accept_tri(t.y, u.y, v.y, uv.y);
-#endif
     return h;
 }
 /* Primary-ray pair records. Every primary ray of a frame starts at the camera (pathTracer.comp:299-302, SceneData
@@ -878,9 +808,6 @@ __device__ __forceinline__ PairHit rayTrianglePair(const Ray& r, const TriPair& 
  * order, so the values are bit-identical) and the first segment of each sample tests its leaves from these records:
  * 51 instead of 68 VALU per pair. 112 B per pair: (e1x, e1y) (e1z, e2x) (e2y, e2z) (oax, oay) (oaz, qx) (qy, qz)
  * (tq, pad), each a float2 {triangle 2j, 2j+1}. */
-#ifndef WCPT_PRIMARY_PAIRS
-#define WCPT_PRIMARY_PAIRS 1
-#endif
 constexpr uint32_t kPrimPairFloat4s = 7;
 constexpr uint32_t kPrimPairRecordBytes = 16u * kPrimPairFloat4s;
 struct TriPairP { v2f e1x, e1y, e1z, e2x, e2y, e2z, oax, oay, oaz, qx, qy, qz, tq; };
@@ -923,22 +850,13 @@ __device__ __forceinline__ PairHit rayTrianglePairP(const Ray& r, const TriPairP
     const v2f uv = u + v;
     PairHit h;
     h.t = t;
-#if WCPT_PAIR_ITAKE
     /* t > 0 is part of the take's integer compare (take_bits) */
     const v2f w = bc2(1.0f) - uv;
     h.hit0 = accept_uvw(u.x, v.x, w.x);
     h.hit1 = accept_uvw(u.y, v.y, w.y);
-#elif WCPT_ACCEPT_MIN3
-    const v2f w = bc2(1.0f) - uv;
-    h.hit0 = accept_tri_w(t.x, u.x, v.x, w.x);
-    h.hit1 = accept_tri_w(t.y, u.y, v.y, w.y);
-#else
-    h.hit0 = accept_tri(t.x, u.x, v.x, uv.x);
-    h.hit1 = accept_tri(t.y, u.y, v.y, uv.y);
-#endif
     return h;
 }
-/* Exact sign pre-reject of a primary pair (WCPT_PRIM_SIGN_SKIP, VERDICT r05 item 3: execute fewer triangle tests).
+/* Exact sign pre-reject of a primary pair (execute fewer triangle tests).
  * The reference's t is RN(tn * RN(1 / det)) (:126, :130), and a take needs t > 0 (:132). The primary records hold tn
  * itself (tq, bit-identical to the test's), and det is the test's first result, so before the rest of the test: when
  * the sign bits of tq and det differ, t is negative, -0 (an underflow) or NaN (a NaN operand) -- never > 0 -- and when
@@ -952,12 +870,6 @@ __device__ __forceinline__ PairHit rayTrianglePairP(const Ray& r, const TriPairP
  * The argument needs only sign(rcp(det)) = sign(det) and rcp(+-0) = +-inf. Both hold for the bare v_rcp_f32 of the fast
  * arithmetic mode as for the corrected reciprocal (the instruction keeps the operand's sign, and a denormal det it may
  * flush is a zero of the same sign), so the fast kernels skip the same way: there t = RN(tq * rcp(det)). */
-#ifndef WCPT_PRIM_SIGN_SKIP
-#define WCPT_PRIM_SIGN_SKIP 1
-#endif
-#ifndef WCPT_PAIR_PREFETCH
-#define WCPT_PAIR_PREFETCH 0
-#endif
 template <int A = kArithExact>
 __device__ __forceinline__ v2f pairP_det(const Ray& r, const TriPairP& p, v2f& px, v2f& py, v2f& pz)
 {
@@ -981,18 +893,9 @@ __device__ __forceinline__ PairHit pairP_finish(const Ray& r, const TriPairP& p,
     const v2f uv = u + v;
     PairHit h;
     h.t = t;
-#if WCPT_PAIR_ITAKE
     const v2f w = bc2(1.0f) - uv;
     h.hit0 = accept_uvw(u.x, v.x, w.x);
     h.hit1 = accept_uvw(u.y, v.y, w.y);
-#elif WCPT_ACCEPT_MIN3
-    const v2f w = bc2(1.0f) - uv;
-    h.hit0 = accept_tri_w(t.x, u.x, v.x, w.x);
-    h.hit1 = accept_tri_w(t.y, u.y, v.y, w.y);
-#else
-    h.hit0 = accept_tri(t.x, u.x, v.x, uv.x);
-    h.hit1 = accept_tri(t.y, u.y, v.y, uv.y);
-#endif
     return h;
 }
 /* whether a lane may take either triangle of the pair: the sign bits of tq and det agree for at least one of them */
@@ -1055,18 +958,11 @@ __device__ __forceinline__ uint32_t leaf_record(uint32_t first, uint32_t count, 
 /* v_mul_u32_u24 (full rate). __umul24 is not enough here: only the low 24 bits of its product are used, so the
  * optimizer drops its 24-bit operand masks and the backend then emits the quarter-rate v_mul_lo_u32 (seen in the ISA
  * of both kernels). */
-#ifndef WCPT_MUL24_ASM
-#define WCPT_MUL24_ASM 1
-#endif
 __device__ __forceinline__ uint32_t mul_u32_u24(uint32_t a, uint32_t b_uniform)
 {
-#if WCPT_MUL24_ASM
     uint32_t r;
     asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "s"(b_uniform), "v"(a));
     return r;
-#else
-    return __umul24(a, b_uniform);
-#endif
 }
 __device__ __forceinline__ uint32_t leaf_record_off24(uint32_t first, uint32_t count, uint32_t lim3)
 {
@@ -1291,14 +1187,6 @@ struct PrivateStack {
     }
 };
 
-#ifndef WCPT_STACK_UNIFORM_FAST
-#define WCPT_STACK_UNIFORM_FAST 0
-#endif
-/* Spill wait in the pop's spill branch (LdsStack::pop): measured c4 -1.2 % alone, c3 -1.4 % alone, and with the
- * deferred hit stores (pt_wavefront.hip WCPT_WF_DEFER_HIT) c3 -2.9 % / c4 -2.8 % (profiles/r05_store_wait_ab.log). */
-#ifndef WCPT_STACK_SPILL_WAIT
-#define WCPT_STACK_SPILL_WAIT 1
-#endif
 /* Entries are packed (node index | t0 bits << 32). The two storage classes are typed by address space so that
  * the compiler emits ds_read/ds_write for the LDS part and scratch_* for the spill instead of merging the two
  * into one flat access. */
@@ -1312,15 +1200,6 @@ struct LdsStack {
     __device__ __forceinline__ bool push(uint32_t i, float t)
     {
         const uint64_t e = (uint64_t)i | ((uint64_t)__float_as_uint(t) << 32);
-#if WCPT_STACK_UNIFORM_FAST
-        /* wave-uniform fast path: no pushing lane has reached the spill region (one compare and a scalar branch
-         * instead of the exec-mask bookkeeping of a divergent if/else) */
-        if (!__ballot(sp >= N)) {
-            base[sp * 64] = e;
-            sp++;
-            return true;
-        }
-#endif
         if (sp < N) {
             base[sp * 64] = e;
         } else if (sp < N + SPILL) {
@@ -1335,20 +1214,16 @@ struct LdsStack {
     {
         sp--;
         uint64_t e;
-#if WCPT_STACK_UNIFORM_FAST
-        if (!__ballot(sp >= N)) {
-            e = base[sp * 64];
-        } else
-#endif
         if (sp < N) {
             e = base[sp * 64];
         } else {
             e = spill[sp - N];
-#if WCPT_STACK_SPILL_WAIT && defined(__gfx9__)
+#if defined(__gfx9__)
             /* wait for the spill load inside its (rare) branch: otherwise the LDS read of the other lanes, which
              * writes the same registers, waits for vmcnt(0) on every pop -- and so for every store still in flight.
              * The immediate is the gfx9 s_waitcnt encoding (gfx950 is gfx9); other generations lay the counters out
-             * differently and get no explicit wait. */
+             * differently and get no explicit wait. Measured c4 -1.2 % alone, c3 -1.4 % alone, and with the deferred
+             * hit stores (pt_wavefront.hip, kModeIdlePend) c3 -2.9 % / c4 -2.8 % (profiles/r05_store_wait_ab.log). */
             __builtin_amdgcn_s_waitcnt(0x0F70); /* vmcnt(0), expcnt/lgkmcnt untouched (gfx9 encoding) */
 #endif
         }
@@ -1447,42 +1322,16 @@ __device__ __forceinline__ DrawGeom draw_geom(const wcpt_draw_command* __restric
  * record's test. Its byte offset with the two acceptance bits in bits 0-1, and both t: the second leaf reuses the
  * values the first computed -- the same test of the same ray on the same record -- and still applies them against
  * its own rec.t in its own order. Reset per segment and per draw (the offsets are relative to a draw's records). */
-#ifndef WCPT_PEEL_CACHE
-#define WCPT_PEEL_CACHE 1
-#endif
 struct PeelCache { uint32_t tag; v2f t; };
 constexpr uint32_t kNoPeel = 0xFFFFFFFFu;
 /* Take the pair's triangles in reference order (2j, then 2j+1; each iff accepted with t < rec.t, strict):
- * the winner is tagged with the record offset (+1 for the second). WCPT_PAIR_MERGE=1 picks the pair's own winner first
- * (the second only when strictly nearer, as the reference's second `<` against the updated rec.t would) and compares
- * that one with rec.t: the same winner, with one compare-select on rec.t's dependency chain per pair instead of two. */
-#ifndef WCPT_PAIR_MERGE
-#define WCPT_PAIR_MERGE 0
-#endif
-#if WCPT_PAIR_ITAKE
-/* rb = bits(rec.t) - 1 (take_bits); hit0/hit1 are the acceptance without t > 0 */
+ * the winner is tagged with the record offset (+1 for the second).
+ * rb = bits(rec.t) - 1 (take_bits); hit0/hit1 are the acceptance without t > 0 */
 __device__ __forceinline__ void pair_take_bits(const PairHit& ph, uint32_t off, uint32_t& rb, uint32_t& tag)
 {
     const uint32_t b0 = take_bits(ph.t.x), b1 = take_bits(ph.t.y);
     if (ph.hit0 && b0 < rb) { rb = b0; tag = off; }
     if (ph.hit1 && b1 < rb) { rb = b1; tag = off + 1u; }
-}
-#endif
-__device__ __forceinline__ void pair_take(const PairHit& ph, uint32_t off, float& rt, uint32_t& tag)
-{
-#if WCPT_PAIR_MERGE
-    const float c0 = ph.hit0 ? ph.t.x : __builtin_inff();
-    const float c1 = ph.hit1 ? ph.t.y : __builtin_inff();
-    const bool second = c1 < c0;
-    const float cb = second ? c1 : c0;
-    if (cb < rt) {
-        rt = cb;
-        tag = off + (second ? 1u : 0u);
-    }
-#else
-    if (ph.hit0 && ph.t.x < rt) { rt = ph.t.x; tag = off; }
-    if (ph.hit1 && ph.t.y < rt) { rt = ph.t.y; tag = off + 1u; }
-#endif
 }
 template <bool COUNT, bool DIAG, bool UNIFORM, bool PRIM, int A = kArithExact>
 __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_t k0, uint32_t kend, float& rt,
@@ -1496,7 +1345,6 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
     };
     /* the peeled pair at `off`, through the per-segment cache */
     auto peeled_at = [&](uint32_t off) {
-#if WCPT_PEEL_CACHE
         PairHit ph;
         if ((pc.tag & ~3u) == off) {
             ph.t = pc.t;
@@ -1508,24 +1356,13 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
             pc.t = ph.t;
         }
         return ph;
-#else
-        (void)pc;
-        return test_at(off);
-#endif
     };
-#if WCPT_PAIR_ITAKE
     uint32_t rb = take_bits(rt); /* rec.t as bits - 1 through the leaf (take_bits) */
-#define WCPT_TAKES(T, I) (take_bits(T) < rb)
-#define WCPT_SET_RT(T) (rb = take_bits(T))
-#else
-#define WCPT_TAKES(T, I) ((T) < rt)
-#define WCPT_SET_RT(T) (rt = (T))
-#endif
     uint32_t k = k0;
     if (k & 1u) {
         const PairHit ph = peeled_at((k >> 1) * kBytes);
         count_tri<COUNT, DIAG>(cnt);
-        if (ph.hit1 && WCPT_TAKES(ph.t.y, 1)) { WCPT_SET_RT(ph.t.y); prim = 3u * k; }
+        if (ph.hit1 && take_bits(ph.t.y) < rb) { rb = take_bits(ph.t.y); prim = 3u * k; }
         k++;
     }
     /* whole pairs: one 32-bit byte-offset induction variable from the draw's record base, and the winner recorded
@@ -1534,7 +1371,6 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
     const uint32_t kfull = kend & ~1u;
     const uint32_t offEnd = (kfull >> 1) * kBytes;
     uint32_t off = (k >> 1) * kBytes, tag = kNoTag;
-#if WCPT_PAIR_UNIFORM
     if (UNIFORM) {
         /* Lanes whose whole-pair range equals the first active lane's (in a coherent wave: all of them) read the
          * records at wave-uniform offsets with scalar loads: they go through the scalar cache (no per-lane
@@ -1550,30 +1386,8 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
             /* the loop counter itself in an SGPR (offU..endU): no per-lane offset arithmetic (70 -> 68 VALU per
              * pair, c2 -1.7 %). A wave-uniform loop like this one was mis-compiled inside the old nested draw loop;
              * in the flat traversal loop it is correct (tools/stack_probe.py) */
-#if WCPT_PAIR_PREFETCH
-            if constexpr (!PRIM) {
-                /* software-pipelined scalar records: the next pair's record is requested before this pair is tested,
-                 * so its scalar-cache latency hides behind the test. The record one past the leaf's whole pairs is
-                 * inside the draw's allocation (runtime: ntri / 2 + 1 pair records) and is never used. */
-                TriPair cur = load_pair_const(pbase, offU);
-                for (uint32_t o = offU; o < endU; o += kBytes) {
-                    const TriPair nxt = load_pair_const(pbase, o + kBytes);
-                    const PairHit ph = rayTrianglePair<A>(ray, cur);
-                    count_tri<COUNT, DIAG>(cnt);
-                    count_tri<COUNT, DIAG>(cnt);
-#if WCPT_PAIR_ITAKE
-                    pair_take_bits(ph, o, rb, tag);
-#else
-                    pair_take(ph, o, rt, tag);
-#endif
-                    cur = nxt;
-                }
-                off = offEnd;
-            } else
-#endif
             for (uint32_t o = offU; o < endU; o += kBytes) {
                 PairHit ph;
-#if WCPT_PRIM_SIGN_SKIP
                 if constexpr (PRIM) {
                     const TriPairP p = load_pairP_const(pbase, o);
                     v2f px, py, pz;
@@ -1589,10 +1403,6 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
                 } else {
                     ph = rayTrianglePair<A>(ray, load_pair_const(pbase, o));
                 }
-#else
-                if constexpr (PRIM) ph = rayTrianglePairP<A>(ray, load_pairP_const(pbase, o));
-                else ph = rayTrianglePair<A>(ray, load_pair_const(pbase, o));
-#endif
 #if WCPT_DUP_PAIR
                 {
                     Ray r2 = ray;
@@ -1606,16 +1416,11 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
 #endif
                 count_tri<COUNT, DIAG>(cnt);
                 count_tri<COUNT, DIAG>(cnt);
-#if WCPT_PAIR_ITAKE
                 pair_take_bits(ph, o, rb, tag);
-#else
-                pair_take(ph, o, rt, tag);
-#endif
             }
             off = offEnd;
         }
     }
-#endif
     for (; off < offEnd; off += kBytes) {
         const PairHit ph = test_at(off);
 #if WCPT_DUP_PAIR
@@ -1629,24 +1434,16 @@ __device__ __forceinline__ void pair_leaf(const Ray& ray, gtri_ptr recs, uint32_
 #endif
         count_tri<COUNT, DIAG>(cnt);
         count_tri<COUNT, DIAG>(cnt);
-#if WCPT_PAIR_ITAKE
         pair_take_bits(ph, off, rb, tag);
-#else
-        pair_take(ph, off, rt, tag);
-#endif
     }
     if (tag != kNoTag) prim = 3u * (2u * (tag / kBytes) + (tag & 1u));
     if (k < kfull) k = kfull;
     if (k < kend) {
         const PairHit ph = peeled_at((k >> 1) * kBytes);
         count_tri<COUNT, DIAG>(cnt);
-        if (ph.hit0 && WCPT_TAKES(ph.t.x, 0)) { WCPT_SET_RT(ph.t.x); prim = 3u * k; }
+        if (ph.hit0 && take_bits(ph.t.x) < rb) { rb = take_bits(ph.t.x); prim = 3u * k; }
     }
-#if WCPT_PAIR_ITAKE
     rt = __uint_as_float(rb + 1u);
-#endif
-#undef WCPT_TAKES
-#undef WCPT_SET_RT
 }
 
 /* Leaf (:164-178): every triangle of the leaf at index positions [curLeft, curLeft + curCount), in index order,
@@ -1660,11 +1457,9 @@ __device__ __forceinline__ void leaf_step(const Ray& ray, const DrawGeom& g, uin
     const uint32_t k0 = leaf_record(curLeft, curCount, g.ntri);
     if (PAIRS && k0 != kNoRecord) {
         const uint32_t kend = k0 + (curCount + 2u) / 3u;
-#if WCPT_PRIMARY_PAIRS
         if (primary && g.ptris != nullptr)
             pair_leaf<COUNT, DIAG, UNIFORM, true, A>(ray, g.ptris, k0, kend, rt, prim, cnt, pc);
         else
-#endif
             pair_leaf<COUNT, DIAG, UNIFORM, false, A>(ray, g.tris, k0, kend, rt, prim, cnt, pc);
     } else {
         for (uint32_t k = 0, j = 0; k < curCount; k += 3, j++) {
@@ -1735,9 +1530,6 @@ __device__ __forceinline__ bool interior_step(const Ray& ray, const DrawGeom& g,
     return false;
 }
 
-#ifndef WCPT_MK_POP_ONCE
-#define WCPT_MK_POP_ONCE 1
-#endif
 /* Pop (:157-162): the next deferred node whose box entry distance is not beyond rec.t; false when none is left. */
 template <bool COUNT, class Stack>
 __device__ __forceinline__ bool pop_step(const DrawGeom& g, Stack& stk, uint32_t& curLeft, uint32_t& curCount, float rt,
@@ -1789,9 +1581,6 @@ __device__ __forceinline__ bool root_step(const Ray& ray, const DrawGeom& g, flo
  * the same too: the megakernel keeps sample 0's and later samples resolve their primary segment from it (render
  * builds for samples > 1 only, a separate instantiation -- keeping the record costs the one-sample kernel 20 VGPRs --
  * and never the COUNT build, which traces every segment as the reference does for the exact counters). */
-#ifndef WCPT_MK_PRIMARY_REUSE
-#define WCPT_MK_PRIMARY_REUSE 1
-#endif
 /* Primary cache (WCPT_OPTION_PRIMARY_CACHE): the same record kept from one frame to the next while camera, frame
  * geometry and scene stand still (primary_cache_key.h has the rule). Render builds only; PC is the launch's mode:
  * kPrimCacheWrite traces as usual and stores the lane's record after the primary segment of sample 0 at `pcache`
@@ -1817,7 +1606,7 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
     float rt = kInfinity;
     uint32_t prim = kNoPrim, primDraw = 0;
     /* a later sample's primary segment, or under the primary cache's read mode every sample's (TraceRay) */
-    if (!COUNT && (WCPT_MK_PRIMARY_REUSE || PC == kPrimCacheRead) && reuse_primary) {
+    if (!COUNT && reuse_primary) {
         rt = prim_rec.x;
         prim = __float_as_uint(prim_rec.y);
         primDraw = __float_as_uint(prim_rec.z);
@@ -1864,7 +1653,6 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
                 mode = curCount > 0 ? kLeaf : kInterior;
             }
             while (mode != kDone) {
-#if WCPT_MK_POP_ONCE
                 if (mode == kPop) {
                     /* one stack entry per iteration (no inner pop loop): a culled entry (:162) keeps the lane popping */
                     if (stk.empty()) {
@@ -1883,11 +1671,6 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
                     }
                     phase_mark(cnt, 2);
                 }
-#else
-                if (mode == kPop)
-                    mode = pop_step<COUNT>(g, stk, curLeft, curCount, rt, cnt, rf) ? (curCount > 0 ? kLeaf : kInterior)
-                                                                                    : kDone;
-#endif
                 if (mode == kInterior)
                     mode = interior_step<COUNT, DIAG>(ray, g, stk, curLeft, curCount, rt, cnt, overflow, rf)
                                ? (curCount > 0 ? kLeaf : kInterior) : kPop;
@@ -1927,7 +1710,7 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
             }
         }
     }
-    if (!COUNT && WCPT_MK_PRIMARY_REUSE && primary && sd.samples > 1u) prim_rec = make_float4(rt, __uint_as_float(prim), __uint_as_float(primDraw), 0.0f);
+    if (!COUNT && primary && sd.samples > 1u) prim_rec = make_float4(rt, __uint_as_float(prim), __uint_as_float(primDraw), 0.0f);
     if (!COUNT && PC == kPrimCacheWrite && primary && !reuse_primary) { /* a traced primary segment: sample 0's */
         uint32_t* const pl = prim_cache_lane<SINGLE>(pcache);
         pl[0] = __float_as_uint(rt);
@@ -1987,18 +1770,12 @@ __device__ __forceinline__ void path_begin(PathState& ps, f3 origin, f3 dir)
     ps.bounce = 0;
 }
 
-#ifndef WCPT_SHADE_SHARED
-#define WCPT_SHADE_SHARED 1
-#endif
 /* The last segment of a pixel's last sample ends the path whatever it samples next: after its emission term
  * (:253) the reference still draws the BSDF sample of :256-280 -- the next direction, transmittance and RNG state --
  * but the loop then exits (:245, :283) and nothing reads them again (the RNG state carries over only into a next
- * sample, :309-310). WCPT_LAST_SEGMENT_SHORTCUT=1 returns right after the emission term there: the same radiance
+ * sample, :309-310). path_shade returns right after the emission term there: the same radiance
  * bits, without the dead RandomDirection, reflection, normalize and 1/direction. The condition is wave-uniform in
  * the megakernel (the lanes of a wave start every sample together). */
-#ifndef WCPT_LAST_SEGMENT_SHORTCUT
-#define WCPT_LAST_SEGMENT_SHORTCUT 1
-#endif
 /* Shading after an Intersect (pathTracer.comp:248-280). Returns true when the path is finished, with its
  * radiance in L: on a miss (:248-249) or when the bounce loop is exhausted (:245, :283). lastSample: this is the
  * pixel's last sample (its RNG state is not read after the path). */
@@ -2017,16 +1794,11 @@ __device__ __forceinline__ bool path_shade(PathState& ps, const Hit& h, uint32_t
     const float emissionStrength = m.emissionStrength;
     const float roughness = m.roughness;
     ps.totalLight = ps.totalLight + (emission * emissionStrength) * ps.transmittance;
-#if WCPT_LAST_SEGMENT_SHORTCUT
     if (lastSample && ps.bounce + 1u > sd.maxBounceCount) { /* the loop's last iteration (:245): nothing below is read */
         L = ps.totalLight;
         return true;
     }
-#else
-    (void)lastSample;
-#endif
 
-#if WCPT_SHADE_SHARED
     /* Both branches of :256-280 end in normalize(base + roughness * RandomDirection(rng)) and a new 1/direction.
      * That tail is shared here, after the dielectric-only part (Fresnel, refract and the :273 rand, which must
      * precede RandomDirection in the lane's RNG sequence), so a wave whose lanes hit both kinds of material runs
@@ -2067,33 +1839,6 @@ __device__ __forceinline__ bool path_shade(PathState& ps, const Hit& h, uint32_t
     }
     ray.direction = dir;
     ray.invDirection = rcp3_a<A>(dir);
-#else
-    if (mtype == WCPT_MATERIAL_METAL) {
-        ray.origin = h.p + h.normal * kBias;
-        const f3 R = reflect(ray.direction, h.normal);
-        const f3 rd = RandomDirection(rng);
-        ray.direction = normalize(R + roughness * rd);
-        ray.invDirection = rcp3(ray.direction);
-        ps.transmittance = ps.transmittance * ld3(m.albedo);
-    } else {
-        const float ior = m.ior;
-        const float etaI = h.front ? 1.0f : ior;
-        const float etaT = h.front ? ior : 1.0f;
-        const float reflectProb = CalculateReflectance(ray.direction, h.normal, etaI, etaT);
-        const f3 R = reflect(ray.direction, h.normal);
-        const f3 T = refract(ray.direction, h.normal, etaI / etaT);
-        bool followReflection = (T.x == 0.0f && T.y == 0.0f && T.z == 0.0f);
-        if (!followReflection) followReflection = (rand_f(rng) <= reflectProb); /* :273 short-circuit */
-        const f3 rd = RandomDirection(rng);
-        ray.direction = normalize((followReflection ? R : T) + roughness * rd);
-        ray.invDirection = rcp3(ray.direction);
-        if (!followReflection && !h.front) {
-            const f3 e = ((ld3(m.absorption) * -1.0f) * m.absorptionStrength) * h.t;
-            ps.transmittance = ps.transmittance * mk3(wcpt_expf(e.x), wcpt_expf(e.y), wcpt_expf(e.z));
-        }
-        ray.origin = h.p + (kBias * h.normal) * sign1(dot(ray.direction, h.normal));
-    }
-#endif
     ps.bounce++;
     if (ps.bounce > sd.maxBounceCount) { /* loop exhausted: no sky term (:283) */
         L = ps.totalLight;

@@ -102,7 +102,7 @@ struct WfState {
     int trace_bpc[3][3][3] = {};   /* trace-kernel blocks per CU by (mode, geometry variant, LDS stack)      */
     int persist_bpc = 0;           /* the path-persistent trace's blocks per CU                             */
     /* queue counters: two sets of {count q0, count q1, trace head, -}; a frame uses set `parity` and its ray generation
-     * zeroes the other set for the next frame (pt_wavefront.hip WCPT_WF_CTR_PARITY); `ctr_fresh` until the first zeroing */
+     * zeroes the other set for the next frame (pt_wavefront.hip wf_init); `ctr_fresh` until the first zeroing */
     uint32_t parity = 0;
     bool ctr_fresh = true;
 };
@@ -119,7 +119,6 @@ struct WfPipes {
     hipStream_t aux[kWfMaxPipes] = {};   /* [1..K-1]: created on first use, on the context's device */
     hipEvent_t fork = nullptr;
     hipEvent_t join[kWfMaxPipes] = {};
-    hipEvent_t ready[kWfMaxPipes] = {};  /* pipeline j's init has run (WCPT_WF_START_TOGETHER) */
     /* frame overlap (WCPT_OPTION_FRAME_OVERLAP): pipelines 1..pending_pipes-1 hold frames the context's stream has not
      * been joined to (wf_join), of a frame of pending_W x pending_rows */
     bool pending = false;
@@ -189,12 +188,8 @@ constexpr int kModeRender = 0, kModeCount = 1, kModeDiag = 2;
 /* Derived triangle records (pt_device.h): triangle k = index positions 3k..3k+2 stored as (a, b - a, c - a);
  * singles: 48 B per triangle; pairs: 80 B per triangle pair (2j, 2j+1). */
 constexpr uint32_t kSingleRecordBytes = 48, kPairRecordBytes = 80;
-/* primary-ray pair records (pt_device.h TriPairP), built with launch_build_primary_pairs; WCPT_PRIMARY_PAIRS=0 turns
- * them off (the device then never finds a primary record address in the table) */
+/* primary-ray pair records (pt_device.h TriPairP), built with launch_build_primary_pairs */
 constexpr uint32_t kPrimPairRecordBytes = 112;
-#ifndef WCPT_PRIMARY_PAIRS
-#define WCPT_PRIMARY_PAIRS 1
-#endif
 /* vertex_count bounds the vertex indices read (0xFFFFFFFF: unknown); a triangle with an index past it gets a NaN
  * record, which no ray accepts. */
 /* Primary-ray pair records (pt_device.h TriPairP) of `npairs` pair records for the camera origin (ox, oy, oz). */

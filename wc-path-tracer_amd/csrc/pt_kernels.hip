@@ -620,7 +620,7 @@ void mk_release(MkState& mk)
 }
 
 /* Longest-first tile order from the costs the renders record (tile time in shader cycles). Measured (round 3,
- * tools/tile_trace.py, 20 frames x 4 interleaved rounds): tile times vary with a coefficient of variation of 0.5-0.66
+ * a per-tile timing build, 20 frames x 4 interleaved rounds): tile times vary with a coefficient of variation of 0.5-0.66
  * across a frame and repeat from frame to frame for a still camera (the same primary rays); starting the longest
  * tiles first leaves the short ones to fill the launch's last round: the Cornell box 0.3863 -> 0.3761 ms, its
  * 270-row block 0.1251 -> 0.1209 ms, the reference's scene 1.486 -> 1.284 ms. Sorted after the first render of a
@@ -699,7 +699,7 @@ template <int SK, bool PAIRS, bool SINGLE, int A>
 static hipError_t launch_mega_arith(const LaunchArgs& a, int pcmode, MkState& mk, hipStream_t stream, uint32_t tilesX,
                                      uint32_t tiles, const uint32_t* list, uint32_t grid)
 {
-    const bool reuse = a.sd.samples > 1u && WCPT_MK_PRIMARY_REUSE;
+    const bool reuse = a.sd.samples > 1u;
     if (pcmode == kPrimaryCacheRead) /* its one-sample form holds the sample count as a constant: only for samples == 1 */
         return a.sd.samples != 1u
                    ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheRead, A>(a, mk, stream, tilesX, tiles, list, grid)

@@ -98,35 +98,14 @@ __device__ __forceinline__ uint32_t block_append(uint32_t* counter, bool pred, u
     return slot;
 }
 
-#ifndef WCPT_WF_PUSH_CULL
-#define WCPT_WF_PUSH_CULL 1
-#endif
-#ifndef WCPT_WF_ANYHIT_LAST
-#define WCPT_WF_ANYHIT_LAST 1
-#endif
 #ifndef WCPT_WF_TAIL_WINDOW
 #define WCPT_WF_TAIL_WINDOW 16 /* rays per wave of the grid: claims for idle lanes only in the queue's last window */
-#endif
-#ifndef WCPT_WF_POP_ONCE
-#define WCPT_WF_POP_ONCE 1
-#endif
-#ifndef WCPT_WF_PRIMARY_REUSE
-#define WCPT_WF_PRIMARY_REUSE 1 /* samples 1.. shade their primary segment from sample 0's record */
-#endif
-#ifndef WCPT_WF_SMALL_LEAVES
-#define WCPT_WF_SMALL_LEAVES 1 /* the fast layout also requires kTriFlagSmallLeaves: packed stack entries need no fetch case */
-#endif
-#ifndef WCPT_WF_LEAF_RECORDS
-#define WCPT_WF_LEAF_RECORDS 1 /* the fast layout also requires kTriFlagLeafRecords: leaf steps need no index path */
 #endif
 /* Path-persistent trace (PERSIST instances, launch_wavefront): one launch runs every segment of its paths. A lane whose
  * ray is done shades it in place (resolve_hit, path_shade, the next segment's sphere loop, or the pixel's store) and
  * goes on with the path's next segment, so no path waits for the slowest ray of its bounce; the wave shades once
  * `refill` of its lanes wait, or when none is tracing. Used where a pipeline's queue is short (row blocks), for one
  * sample per pixel. */
-#ifndef WCPT_WF_CTR_PARITY
-#define WCPT_WF_CTR_PARITY 1
-#endif
 #ifndef WCPT_WF_PERSIST_WAVES
 #define WCPT_WF_PERSIST_WAVES 4
 #endif
@@ -147,7 +126,7 @@ __global__ __launch_bounds__(kShadeBlock) void wf_init(const wcpt_scene_data sd,
                                                        uint32_t* __restrict__ zero_next)
 {
     /* the queue counters of the pipeline's next frame (the other counter set, unused by this frame): zeroed here, so a
-     * frame needs no memset launch of its own (WCPT_WF_CTR_PARITY) */
+     * frame needs no memset launch of its own */
     if (zero_next && blockIdx.x == 0 && threadIdx.x < 4u) zero_next[threadIdx.x] = 0u;
     __shared__ uint32_t s_wave[kShadeBlock / 64], s_base;
     Counters cnt = {};
@@ -203,25 +182,9 @@ enum : uint32_t { kModeInterior = 0, kModeLeaf = 1, kModePop = 2, kModeDone = 3,
 /* Deferred hit stores: a lane whose ray is done keeps its (t, primitive) record in registers (kModeIdlePend, an idle
  * lane) and the wave writes the records when it next refills, or at its exit. On gfx9 a store counts in vmcnt, and the
  * loop's in-order vmcnt waits (the pop's, the node fetch's) would otherwise wait for it on the next iteration.
- * Measured with the in-branch spill wait (pt_device.h WCPT_STACK_SPILL_WAIT), 2 alternating rounds
+ * Measured with the in-branch spill wait (pt_device.h LdsStack::pop), 2 alternating rounds
  * (profiles/r05_store_wait_ab.log): c3 4.708-4.714 against 4.848-4.856 ms (-2.9 %), c4 199.5 against 205.3 ms
  * (-2.8 %); alone c3 -2.0 %, c4 -2.7 %. */
-#ifndef WCPT_WF_DEFER_HIT
-#define WCPT_WF_DEFER_HIT 1
-#endif
-
-#ifndef WCPT_WF_TRACE_SHARE
-#define WCPT_WF_TRACE_SHARE 1
-#endif
-#ifndef WCPT_WF_REC_OFF24
-#define WCPT_WF_REC_OFF24 1
-#endif
-#ifndef WCPT_WF_PAIR_RSRC
-#define WCPT_WF_PAIR_RSRC 1
-#endif
-#ifndef WCPT_WF_GEO_FAST
-#define WCPT_WF_GEO_FAST 1
-#endif
 struct Geom {
     gtri_ptr tris;
     uint32_t ntri;
@@ -243,7 +206,7 @@ __device__ __forceinline__ Geom load_geom(const wcpt_draw_command* __restrict__ 
     g.tris = (gtri_ptr)(uintptr_t)tri_records[kTriTableWords * d];      /* single records */
     g.ntri = (uint32_t)tri_records[kTriTableWords * d + 2u];
     g.packed = (tri_records[kTriTableWords * d + 3u] & kTriFlagPackedRefs) != 0u;
-    g.idx24 = WCPT_WF_REC_OFF24 && (tri_records[kTriTableWords * d + 3u] & kTriFlagIndex24) != 0u;
+    g.idx24 = (tri_records[kTriTableWords * d + 3u] & kTriFlagIndex24) != 0u;
     g.lim3 = 3u * g.ntri;
     g.bvh = as_nodes(draws[d].bvhBuffer);
     g.indices = as_u32(draws[d].indexBuffer);
@@ -360,7 +323,7 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
         /* refill <= 64 (wcpt_set_option), so "every lane idle" is included in popcount >= refill; all 64 lanes stay in
          * the loop until the wave leaves it */
         if (!drained && (uint32_t)__popcll(need) >= refill) {
-            if (WCPT_WF_DEFER_HIT && mode == kModeIdlePend) {
+            if (mode == kModeIdlePend) {
                 b.hit[p] = make_float4(rt, __uint_as_float(prim), __uint_as_float(primDraw), 0.0f);
                 mode = kModeIdle;
             }
@@ -390,17 +353,13 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
                 if (take) {
                     p = b.order ? b.order[lo + rank] : lo + rank;   /* input slot: consecutive lanes, consecutive slots */
                     const float4 r0 = b.in.ray0[p];
-#if WCPT_WF_ANYHIT_LAST
                     const float4 r1 = b.in.ray1[p];
                     /* path_shade's last-segment shortcut keeps only the material of this segment's hit, and every
                      * triangle carries material 0 (:175): whether some triangle is accepted below the sphere loop's
                      * rec.t is all that is read. Up to the first acceptance the traversal is the reference's, so the
                      * ray finishes there; its lane takes the next queued ray. */
-                    any = !COUNT && WCPT_LAST_SEGMENT_SHORTCUT && __float_as_uint(r1.z) + 1u > sd.maxBounceCount &&
+                    any = !COUNT && __float_as_uint(r1.z) + 1u > sd.maxBounceCount &&
                           __float_as_uint(r1.w) + 1u == sd.samples;
-#else
-                    const float2 r1 = reinterpret_cast<const float2*>(b.in.ray1)[2u * p];
-#endif
                     const float4 pr = b.in.pre[p];
                     ray.origin = mk3(r0.x, r0.y, r0.z);
                     ray.direction = mk3(r0.w, r1.x, r1.y);
@@ -426,7 +385,6 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
              * its first triangle in the same iteration (measured 1.4% faster than leaf -> interior -> pop). Each
              * lane still executes exactly the reference's sequence of steps. */
             if (mode == kModePop) {
-#if WCPT_WF_POP_ONCE
                 /* one stack entry per iteration: a culled entry (:162) leaves the lane in pop mode */
                 if (stk.empty()) {
                     if (SINGLE) {
@@ -441,29 +399,10 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
                     stk.pop(ni, t0);
                     ref_pop<COUNT>(rf);
                     if (!(t0 > rt)) {
-                        const uint2 lc = (GEO >= 2 && WCPT_WF_SMALL_LEAVES) ? node_ref_lc_small(ni)
-                                                                            : node_ref_lc(g.packed, g.bvh, ni);
+                        const uint2 lc = (GEO >= 2) ? node_ref_lc_small(ni) : node_ref_lc(g.packed, g.bvh, ni);
                         cursor_from(lc.x, lc.y, g, ca, cb, cr, mode);
                     }
                 }
-#else
-                bool found = false;
-                while (!stk.empty()) {
-                    uint32_t ni;
-                    float t0;
-                    stk.pop(ni, t0);
-                    ref_pop<COUNT>(rf);
-                    if (t0 > rt) continue;
-                    const uint2 lc = node_ref_lc(g.packed, g.bvh, ni);
-                    cursor_from(lc.x, lc.y, g, ca, cb, cr, mode);
-                    found = true;
-                    break;
-                }
-                if (!found) {
-                    d++;
-                    start_draw();
-                }
-#endif
             }
             /* the interior step on the fetched child pair (:164-200) */
             auto interior_step = [&](const NodeV& L, const NodeV& R) {
@@ -486,10 +425,10 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
                  * only shrinks, so the render build does not push it (the counting build keeps the reference's
                  * pushes and pops). */
                 const float farT0 = leftFirst ? r0 : l0;
-                if (passFar && (COUNT || !WCPT_WF_PUSH_CULL || !(farT0 > rt))) {
+                if (passFar && (COUNT || !(farT0 > rt))) {
                     const NodeV& F = leftFirst ? R : L;
-                    const uint32_t fref = (GEO >= 2 && WCPT_WF_SMALL_LEAVES) ? node_ref_small(F.b.z, F.b.w)
-                                                                            : node_ref(g.packed, leftFirst ? ca + 1 : ca, F.b.z, F.b.w);
+                    const uint32_t fref = (GEO >= 2) ? node_ref_small(F.b.z, F.b.w)
+                                                     : node_ref(g.packed, leftFirst ? ca + 1 : ca, F.b.z, F.b.w);
                     if (!stk.push(fref, farT0))
                         overflow = true;
                 }
@@ -523,7 +462,7 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
                 return tri_from_indices(g.indices, g.vertices, ca, draw_vertex_count(tri_records, SINGLE ? 0u : d));
             };
             diag_mark<DIAG>(tim, tprev, 3); /* pop */
-            if (GEO == 3 && WCPT_WF_PAIR_RSRC && WCPT_WF_LEAF_RECORDS) {
+            if (GEO == 3) {
                 /* one fetch round per iteration (GEO 3, wf_fetch_once): the child pair of an interior lane and the
                  * triangle of a leaf lane are both issued before either is waited for; a lane that descends into a leaf
                  * tests it next iteration */
@@ -539,7 +478,7 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
             } else {
             if (mode == kModeInterior) {
                 NodeV L, R;
-                if (WCPT_WF_PAIR_RSRC && (GEO >= 2 || g.nodes)) {
+                if (GEO >= 2 || g.nodes) {
                     load_pair_rsrc(g.rsrc, ca, L, R);
                 } else {
                     L = load_node(g.bvh, ca);
@@ -551,7 +490,7 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
             if (mode == kModeLeaf) {
                 /* one triangle per step, from the single records (pair records measured slower here: most
                  * atrium leaves hold 1-2 triangles, and the wider record costs fetch bytes and VGPRs) */
-                if (GEO >= 2 && WCPT_WF_LEAF_RECORDS) {
+                if (GEO >= 2) {
                     /* every leaf triangle has its record (kTriFlagLeafRecords); the load goes through a buffer resource
                      * bounded by the draw's records, so a BVH rewritten behind the runtime's cache (wcpt.h
                      * WCPT_OPTION_TRIANGLE_CACHE) reads zeros -- a triangle no ray accepts -- instead of past them */
@@ -567,11 +506,8 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
                 /* Intersect result; wf_shade rebuilds the winner's normal and material (:204-208) */
                 if (PERSIST) {
                     mode = kModeShade;
-                } else if (WCPT_WF_DEFER_HIT) {
-                    mode = kModeIdlePend;
                 } else {
-                    b.hit[p] = make_float4(rt, __uint_as_float(prim), __uint_as_float(primDraw), 0.0f);
-                    mode = kModeIdle;
+                    mode = kModeIdlePend; /* the record is stored at the wave's next refill or exit */
                 }
                 ref_segment_end<COUNT>(cnt);
             }
@@ -601,10 +537,9 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
                         ray = ps.ray;
                         rt = rt0;
                         prim = prim0;
-                        /* the queue-fetch path's guard (:392): any-hit only where that build option is on, and never
-                         * in a counting pass (which walks the reference's full closest-hit traversal) */
-                        any = !COUNT && WCPT_WF_ANYHIT_LAST && WCPT_LAST_SEGMENT_SHORTCUT &&
-                              ps.bounce + 1u > sd.maxBounceCount && sample + 1u == sd.samples;
+                        /* the queue-fetch path's guard: never any-hit in a counting pass (which walks the reference's
+                         * full closest-hit traversal) */
+                        any = !COUNT && ps.bounce + 1u > sd.maxBounceCount && sample + 1u == sd.samples;
                         d = 0;
                         start_draw();
                     } else {
@@ -630,7 +565,7 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
             }
         }
     }
-    if (WCPT_WF_DEFER_HIT && mode == kModeIdlePend)
+    if (mode == kModeIdlePend)
         b.hit[p] = make_float4(rt, __uint_as_float(prim), __uint_as_float(primDraw), 0.0f);
     if (overflow) atomicOr(status, 1u);
     flush_counters<COUNT>(cnt, counters);
@@ -642,9 +577,6 @@ void wf_trace(const wcpt_scene_data sd, const wcpt_draw_command* __restrict__ dr
 }
 
 /* ---- shade ------------------------------------------------------------------------------------------ */
-#ifndef WCPT_SHADE_PREFETCH
-#define WCPT_SHADE_PREFETCH 0 /* measured +0.8 % on c3, +0.7 % on c4: off */
-#endif
 /* One input queue slot of wf_shade: pixel, ray, light, transmittance and the trace's Intersect record. */
 struct PathIn {
     uint32_t pix;
@@ -676,24 +608,13 @@ __global__ __launch_bounds__(kShadeBlock) void wf_shade(const wcpt_scene_data sd
     const uint32_t n = *b.count_in;
     Counters cnt = {};
     const uint32_t stride = gridDim.x * blockDim.x;
-#if WCPT_SHADE_PREFETCH
-    /* The path state of the thread's next queue slot is loaded before the current one is shaded: the streams (path
-     * state in queue order, coalesced) have one iteration of the grid-stride loop to arrive instead of stalling its
-     * start, and the dependent gathers of the current path (normal, material) overlap them. */
-    PathIn nxt = load_path_in(b, blockIdx.x * blockDim.x + threadIdx.x, n);
-#endif
     for (uint32_t base = blockIdx.x * blockDim.x; base < n; base += stride) {
         const uint32_t w = base + threadIdx.x;
         bool cont = false;
         uint32_t p = 0, sample = 0, seed = 0, prim0 = kNoPrim;
         float rt0 = kInfinity;
         PathState ps;
-#if WCPT_SHADE_PREFETCH
-        const PathIn cur = nxt;
-        nxt = load_path_in(b, w + stride, n);
-#else
         const PathIn cur = load_path_in(b, w, n);
-#endif
         if (w < n) {
             p = cur.pix;                         /* slot w of the compacted input queue */
             const float4 r0 = cur.r0, r1 = cur.r1, li = cur.li, tr = cur.tr;
@@ -709,7 +630,7 @@ __global__ __launch_bounds__(kShadeBlock) void wf_shade(const wcpt_scene_data sd
              * the same too: sample 0's is kept by pixel and later samples shade their primary segment from it
              * without tracing it again (render build only: the COUNT build traces every segment, as the reference
              * does, for the exact counters). */
-            const bool reuse = !COUNT && WCPT_WF_PRIMARY_REUSE && sd.samples > 1u;
+            const bool reuse = !COUNT && sd.samples > 1u;
             if (reuse && ps.bounce == 0u && sample == 0u) b.prim_hit[p] = hi;
             float4 h4 = hi;
             f3 result = mk3(0.0f, 0.0f, 0.0f);
@@ -817,7 +738,7 @@ hipError_t wf_reserve(WfState& s, uint32_t paths)
         s.soa[k].pix = u + P;
         u += 2 * P;
     }
-    s.ctr = u; /* two sets of [0] count q0, [1] count q1, [2] trace head, [3] - (WCPT_WF_CTR_PARITY) */
+    s.ctr = u; /* two sets of [0] count q0, [1] count q1, [2] trace head, [3] - */
     s.diag = reinterpret_cast<unsigned long long*>(reinterpret_cast<uintptr_t>(s.ctr + 8 + 7) & ~uintptr_t(7));
     s.parity = 0;
     s.ctr_fresh = true;
@@ -878,7 +799,6 @@ void wf_release(WfPipes& w)
         wf_release(w.pipe[j]);
         if (w.aux[j]) (void)hipStreamDestroy(w.aux[j]);
         if (w.join[j]) (void)hipEventDestroy(w.join[j]);
-        if (w.ready[j]) (void)hipEventDestroy(w.ready[j]);
     }
     if (w.fork) (void)hipEventDestroy(w.fork);
     if (w.result) (void)hipFree(w.result);
@@ -993,7 +913,7 @@ static hipError_t wf_dispatch(int mode, int geo, int ldsn, bool query, int& bpc,
 static int wf_geo(const LaunchArgs& a, int mode, int ldsn)
 {
     if (a.sd.drawCommandCount != 1) return 0;
-    return (WCPT_WF_GEO_FAST && a.wf_fast && mode == kModeRender && ldsn == 10) ? 2 : 1;
+    return (a.wf_fast && mode == kModeRender && ldsn == 10) ? 2 : 1;
 }
 
 /* One fetch round per trace iteration (GEO 3) or two (GEO 2: a lane that descends into a leaf tests its first
@@ -1042,27 +962,20 @@ static hipError_t pipe_begin(const LaunchArgs& a, int mode, WfState& s, const Wf
     hipError_t e = wf_reserve(s, P);
     if (e != hipSuccess) return e;
     const bool count = mode != kModeRender;
-    /* The queue counters must start at zero. WCPT_WF_CTR_PARITY: the pipeline alternates between two counter sets,
-     * and each frame's wf_init zeroes the set the next frame uses -- the frames of one pipeline run in order on its
-     * stream (and a render's pipelines join before the next render forks), so the previous frame, the only other user
-     * of that set, has finished; only a fresh allocation is zeroed with a memset. Otherwise one memset per pipeline
-     * and frame (a fill kernel launch in the pipeline's chain). */
-    uint32_t* ctr = s.ctr;
-    uint32_t* zero_next = nullptr;
-#if WCPT_WF_CTR_PARITY
+    /* The queue counters must start at zero. The pipeline alternates between two counter sets, and each frame's
+     * wf_init zeroes the set the next frame uses -- the frames of one pipeline run in order on its stream (and a
+     * render's pipelines join before the next render forks), so the previous frame, the only other user of that set,
+     * has finished; only a fresh allocation is zeroed with a memset, instead of one memset per pipeline and frame (a
+     * fill kernel launch in the pipeline's chain). */
     if (s.ctr_fresh) {
         e = hipMemsetAsync(s.ctr, 0, 8 * sizeof(uint32_t), stream);
         if (e != hipSuccess) return e;
         s.ctr_fresh = false;
         s.parity = 0;
     }
-    ctr = s.ctr + 4u * s.parity;
-    zero_next = s.ctr + 4u * (s.parity ^ 1u);
+    uint32_t* ctr = s.ctr + 4u * s.parity;
+    uint32_t* zero_next = s.ctr + 4u * (s.parity ^ 1u);
     s.parity ^= 1u;
-#else
-    e = hipMemsetAsync(s.ctr, 0, 4 * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-#endif
     b.in = s.soa[0];
     b.out = s.soa[1];
     b.result = result;
@@ -1110,7 +1023,7 @@ static hipError_t pipe_iterate(const LaunchArgs& a, int mode, WfState& s, uint32
     /* each iteration advances every live path by one traced segment; a path needs <= samples*(maxBounce+1), or
      * with the primary records reused (wf_shade) maxBounce+1 for sample 0 and maxBounce for each later sample */
     uint64_t iters = (uint64_t)a.sd.samples * ((uint64_t)a.sd.maxBounceCount + 1ull);
-    if (WCPT_WF_PRIMARY_REUSE && mode == kModeRender && a.sd.samples > 1u)
+    if (mode == kModeRender && a.sd.samples > 1u)
         iters = (uint64_t)a.sd.maxBounceCount + 1ull + (uint64_t)(a.sd.samples - 1u) * a.sd.maxBounceCount;
     if (iters > (1ull << 20)) iters = 1ull << 20; /* bounded; WCPT documents the cap */
     for (uint64_t it = 0; it < iters; it++) {
@@ -1128,10 +1041,6 @@ static hipError_t pipe_iterate(const LaunchArgs& a, int mode, WfState& s, uint32
     }
     return hipSuccess;
 }
-
-#ifndef WCPT_WF_START_TOGETHER
-#define WCPT_WF_START_TOGETHER 0
-#endif
 
 hipError_t wf_join(WfPipes& w, hipStream_t stream)
 {
@@ -1210,19 +1119,17 @@ hipError_t launch_wavefront(const LaunchArgs& a, int mode, WfPipes& w, int pipes
     if (sort_rays || mode == kModeDiag) K = 1; /* one sort scratch and one diagnostics block */
     const uint32_t tiles = tilesX * tilesY;
     if (K > tiles) K = tiles;
-#if WCPT_WF_TRACE_SHARE
     /* each pipeline's persistent trace grid holds 1/K of the resident-wave slots, so the K traces run side by side
      * instead of the first one taking every slot and the others only filling its tail (c3 6.58 -> 6.16 ms with two
      * pipelines; 5/8 or 3/4 of the slots per pipeline measured equal, 7/16 slower) */
     if (K > 1) trace_grid = trace_grid / K > 0 ? trace_grid / K : 1u;
-#endif
     const uint32_t persist_grid = persist ? max(1u, persist_full / K) : 0u;
     /* Frame overlap (WCPT_OPTION_FRAME_OVERLAP; the megakernel's in pt_kernels.hip launch_megakernel): pipeline j
      * owns the tiles t % K == j, so while K and the frame's tiles stay, this render's pipelines need not wait for the
      * previous render's other pipelines -- each continues on its own stream, and the context's stream is joined to
      * them only when another entry point needs it (wf_join). On the per-bounce launches that recovers the frame's
      * ragged end (c3: its three pipelines end 0.3-0.5 ms apart, profiles/r06_c3_frame_timeline.log). */
-    const bool cont = overlap != 0 && K > 1 && !WCPT_WF_START_TOGETHER && mode == kModeRender && w.pending &&
+    const bool cont = overlap != 0 && K > 1 && mode == kModeRender && w.pending &&
                       w.pending_pipes == K && w.pending_W == a.W && w.pending_rows == a.rows &&
                       w.pending_persist == (persist_grid != 0);
     if (w.pending && !cont) {
@@ -1264,17 +1171,6 @@ hipError_t launch_wavefront(const LaunchArgs& a, int mode, WfPipes& w, int pipes
     hipError_t first = hipSuccess;
     for (uint32_t j = 0; j < K && first == hipSuccess; j++)
         first = pipe_begin(a, mode, w.pipe[j], s0, w.result, w.result + w.result_capacity, j, K, cus, j == 0 ? stream : w.aux[j], bs[j]);
-    if (WCPT_WF_START_TOGETHER && first == hipSuccess) {
-        /* every pipeline's first trace waits for all the inits: the persistent trace grids then start on an idle
-         * chip together instead of the first one being placed around the other pipelines' init blocks */
-        for (uint32_t j = 0; j < K && first == hipSuccess; j++) {
-            if (!w.ready[j]) first = hipEventCreateWithFlags(&w.ready[j], hipEventDisableTiming);
-            if (first == hipSuccess) first = hipEventRecord(w.ready[j], j == 0 ? stream : w.aux[j]);
-        }
-        for (uint32_t j = 0; j < K && first == hipSuccess; j++)
-            for (uint32_t i = 0; i < K && first == hipSuccess; i++)
-                if (i != j) first = hipStreamWaitEvent(j == 0 ? stream : w.aux[j], w.ready[i], 0);
-    }
     for (uint32_t j = 0; j < K && first == hipSuccess; j++)
         first = pipe_iterate(a, mode, w.pipe[j], j, K, false, ldsn, cus, trace_grid, shade_grid, persist_grid,
                              j == 0 ? stream : w.aux[j], bs[j]);

@@ -108,8 +108,6 @@ constexpr double kPairMinTrianglesPerLeaf = 4.0;
 /* Largest triangle count of a draw whose pair records are used: 40 B per triangle must stay addressable with 32-bit
  * byte offsets (2^26 triangles = 2.5 GiB of pair records); larger draws use single records. */
 constexpr uint64_t kPairMaxTriangles = 1ull << 26;
-/* Primary-ray pair records for the megakernel (pt_device.h WCPT_PRIMARY_PAIRS) */
-constexpr bool kPrimaryPairs = WCPT_PRIMARY_PAIRS != 0;
 
 /* Bytes per pixel of a gather payload format (wcpt.h WCPT_PAYLOAD_*) */
 uint64_t payload_pixel_bytes(uint32_t format) { return format == WCPT_PAYLOAD_DISPLAY_RGBA8 ? 4u : 4ull * format; }
@@ -553,7 +551,7 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
     ctx->kernel_run = ctx->kernel != WCPT_KERNEL_AUTO ? ctx->kernel
                                                       : (a.pair_records || n == 0 ? WCPT_KERNEL_MEGAKERNEL : WCPT_KERNEL_WAVEFRONT);
     /* primary-ray pair records (megakernel with pair records): derived once per camera position and records build */
-    const bool want_primary = kPrimaryPairs && a.pair_records && ctx->kernel_run == WCPT_KERNEL_MEGAKERNEL;
+    const bool want_primary = a.pair_records && ctx->kernel_run == WCPT_KERNEL_MEGAKERNEL;
     uint32_t origin[3];
     std::memcpy(origin, sd.position, sizeof(origin));
     for (uint32_t d = 0; d < n; d++) {
