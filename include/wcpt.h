@@ -159,6 +159,18 @@ extern "C" {
  * application resets renderedFramesCount to 0 (as the reference's editor does whenever something moves).
  * Same results. Added under ABI 4. */
 #define WCPT_OPTION_PRIMARY_CACHE 16
+/* Split renders (megakernel). A wave keeps issuing a segment's traversal while any of its 64 paths is alive, and in an
+ * open scene paths end bounce by bounce. k >= 1: a one-sample render on the LDS stack runs as two launches on the same
+ * stream -- the kernel up to segment k (segments count from 0, the primary one), whose surviving paths go to a queue of
+ * 56 bytes per pixel of the context's rows (allocated when a render first splits), and a launch that finishes them one
+ * per lane in full waves. k > maxBounceCount, samples > 1 and WCPT_OPTION_STACK 0 render in one launch. 0: never. -1
+ * (default): automatic -- before segment 3 (or maxBounceCount, if less) for renders of 3 rounds of resident waves or
+ * more with maxBounceCount >= 2 (a 1920x1080 frame or its halves, not its 4- or 8-way blocks) of a scene with at most
+ * 64 triangles: the second launch's waves hold paths of unrelated tiles, which costs a larger mesh more than the
+ * fuller waves save (the Cornell box -3.7 %, the reference's scene +6 % when forced; csrc/mk_split_rule.h has the
+ * measurements). Values outside -1..15 are refused. Same results.
+ * Added under ABI 4. */
+#define WCPT_OPTION_MK_SPLIT 18
 
 /* ---- options that change results (wcpt_set_option) ---------------------------------------------------------- */
 /* Arithmetic of the megakernel's render launches. WCPT_ARITH_EXACT (0, default): the reference's operand order, unfused,
@@ -406,6 +418,9 @@ int      wcpt_sync(wcpt_context* ctx);
 /* How many renders of the context stored (*writes) and read (*reads) the primary cache (WCPT_OPTION_PRIMARY_CACHE)
  * since it was created; either pointer may be null. Host only. Added under ABI 4. */
 int      wcpt_primary_cache_stats(wcpt_context* ctx, uint64_t* writes, uint64_t* reads);
+/* How many renders of the context ran as two launches (WCPT_OPTION_MK_SPLIT) since it was created. Host only. Added
+ * under ABI 4. */
+int      wcpt_mk_split_stats(wcpt_context* ctx, uint64_t* renders);
 /* Same frame through the instrumented kernel: counts the reference algorithm's work.
  * Does not write the image. Synchronous. */
 int      wcpt_render_counters(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t materials,

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/wcpt.h"
+#include "mk_split_rule.h"
 #include "primary_cache_key.h"
 #include "row_map.h"
 
@@ -28,6 +29,7 @@ struct LaunchArgs {
     const wcpt_sphere* spheres;
     const wcpt_draw_command* draws;
     const uint64_t* tri_records; /* device table [drawCommandCount] of {singles, pairs, triangle count, -} */
+    uint64_t triangles = 0;      /* of all draw commands (the split rule's input, mk_split_rule.h) */
     bool pair_records;           /* megakernel: leaf tests on pair records (fat leaves) instead of singles */
     uint32_t wf_refill;          /* wavefront trace: idle lanes that trigger a ray fetch (1..64) */
     uint32_t wf_refill_persist;  /* the path-persistent trace's refill and shading-batch threshold (1..64) */
@@ -36,6 +38,7 @@ struct LaunchArgs {
     bool wf_fast;                /* wavefront trace: draw 0 has packed stack refs, 24-bit record offsets, leaves of < 255
                                     index positions on derived records (kTriFlagSmallLeaves, kTriFlagLeafRecords) and a known
                                     node count (table flags 1|2|4|8, word 2 high half > 0) */
+    int mk_split = kMkSplitAuto;  /* megakernel render launches: WCPT_OPTION_MK_SPLIT (mk_split_rule.h) */
     int arith = WCPT_ARITH_EXACT; /* megakernel render launches: WCPT_ARITH_FAST takes the fast instances (WCPT_OPTION_ARITH) */
     uint32_t mk_tile_order;      /* static megakernel: 0 XCD-banded, 1 scattered, 2 auto, 3-6 striped bands (WCPT_OPTION_MK_TILE_ORDER) */
     float4* image;
@@ -167,6 +170,15 @@ struct MkState {
     bool prim_valid = false;
     PrimaryCacheKey prim_key = {};
     uint64_t prim_writes = 0, prim_reads = 0; /* renders that took each instantiation (wcpt_primary_cache_stats) */
+    /* Split renders (WCPT_OPTION_MK_SPLIT, mk_split_rule.h): the queues between the head and the tail launch, allocated
+     * when a render first splits: split_entries entries of kMkSplitEntryBytes, then per pipe two counter sets of
+     * kMkSplitCounterWords u32; a pipe's frame counts in set split_parity[p] and its tail zeroes the other for the pipe's
+     * next frame. */
+    void* split_mem = nullptr;
+    uint64_t split_entries = 0;
+    uint32_t* split_ctr = nullptr;            /* [pipe][2][kMkSplitCounterWords] */
+    uint32_t split_parity[2] = {0u, 0u};
+    uint64_t split_renders = 0;               /* renders that ran as head + tail (wcpt_mk_split_stats) */
 };
 constexpr uint32_t kMkPipes = 2;
 void mk_release(MkState& mk);

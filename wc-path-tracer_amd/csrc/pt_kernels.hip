@@ -65,8 +65,27 @@ __device__ __forceinline__ void tile_of_block(uint32_t tilesX, uint32_t tilesTot
     ty = t / tilesX;
 }
 
+/* The end of a pixel (pathTracer.comp:312-323): the mean of the samples' radiance `result`, accumulated into the
+ * image's value `old` (read early by the caller) and stored. Shared by the whole kernel, the head and the tail. */
+__device__ __forceinline__ void accumulate_store(const wcpt_scene_data& sd, float4* __restrict__ image,
+                                                 float* __restrict__ wire, uint32_t wire_ch, const RowMap& wm, uint32_t W,
+                                                 uint32_t lx, uint32_t ly, float4 old, f3 result)
+{
+    result = result / (float)sd.samples; /* :312 */
+    f3 acc;
+    if (sd.renderedFramesCount == 0) { /* :318 — the loaded value would be discarded */
+        acc = result;
+    } else {
+        const float4 o = old;                                             /* :314 */
+        const float weight = 1.0f / (float)(sd.renderedFramesCount + 1u); /* :316 */
+        const float iw = 1.0f - weight;
+        acc = mk3(o.x * iw + result.x * weight, o.y * iw + result.y * weight, o.z * iw + result.z * weight);
+    }
+    store_pixel(image, wire, wire_ch, wm, W, lx, ly, acc); /* :323 */
+}
+
 /* Shade one pixel (pathTracer.comp:290-323) with the given traversal stack. */
-template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A, class Stack>
+template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A, int STAGE, class Stack>
 __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcpt_material* __restrict__ mats,
                                             const wcpt_sphere* __restrict__ spheres,
                                             const wcpt_draw_command* __restrict__ draws,
@@ -74,7 +93,8 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
                                             float* __restrict__ wire, uint32_t wire_ch,
                                             uint32_t W, uint32_t H, const RowMap& rm, const RowMap& wm, uint32_t lx,
                                             uint32_t ly, Stack& stk, Counters& cnt, bool& overflow,
-                                            uint32_t* __restrict__ pcache)
+                                            uint32_t* __restrict__ pcache,
+                                            const typename StageQueue<STAGE>::type& q)
 {
     const uint32_t x = lx, y = frame_row(rm, ly); /* the frame row: a row block or interleaved stripes (row_map.h) */
     const f3 dir = primary_direction(sd, x, y, W, H);
@@ -97,14 +117,26 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
     }
     /* the one-sample read build (launch_mega_render) has its sample count as a constant: the record then dies at its one
      * use instead of staying live across a sample loop (intersect: 20 VGPRs) */
-    const uint32_t samples = (PC == kPrimCacheRead && !REUSE) ? 1u : sd.samples;
+    /* so has a head launch (STAGE; the runtime splits one-sample renders only) */
+    const uint32_t samples = ((PC == kPrimCacheRead && !REUSE) || STAGE == kStageHead) ? 1u : sd.samples;
+    bool appended = false; /* head: the path went to the tail's queue, and the tail stores this pixel */
+    const SplitQueue* qp = nullptr;
+    if constexpr (STAGE == kStageHead) qp = &q;
     for (uint32_t s = 0; s < samples; s++) { /* :309-310, all samples share the primary ray */
         Ray r;
         r.origin = origin;
         r.direction = dir;
         r.invDirection = rcp3(dir);
-        result = result + TraceRay<COUNT, DIAG, PAIRS, SINGLE, Stack, REUSE, PC, A>(r, seed, sd, mats, spheres, draws, tri_records, stk, cnt, overflow,
-                                                       s + 1u == samples, prim_rec, s > 0u, pcache);
+        if constexpr (STAGE == kStageHead)
+            result = result + TraceRay<COUNT, DIAG, PAIRS, SINGLE, Stack, REUSE, PC, A, STAGE>(r, seed, sd, mats, spheres, draws, tri_records, stk, cnt, overflow,
+                                                           s + 1u == samples, prim_rec, s > 0u, pcache, qp,
+                                                           (uint32_t)((size_t)ly * W + lx), &appended);
+        else
+            result = result + TraceRay<COUNT, DIAG, PAIRS, SINGLE, Stack, REUSE, PC, A>(r, seed, sd, mats, spheres, draws, tri_records, stk, cnt, overflow,
+                                                           s + 1u == samples, prim_rec, s > 0u, pcache);
+    }
+    if constexpr (STAGE == kStageHead) {
+        if (appended) return;
     }
     if (PC == kPrimCacheWrite && REUSE) { /* this build (samples > 1) holds sample 0's record in prim_rec (TraceRay) */
         uint32_t* const pl = prim_cache_lane<SINGLE>(pcache);
@@ -112,19 +144,7 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
         pl[1] = __float_as_uint(prim_rec.y);
         if (!SINGLE) pl[2] = __float_as_uint(prim_rec.z);
     }
-    result = result / (float)sd.samples; /* :312 */
-    if (!COUNT) {
-        f3 acc;
-        if (sd.renderedFramesCount == 0) { /* :318 — the loaded value would be discarded */
-            acc = result;
-        } else {
-            const float4 o = old;                                             /* :314 */
-            const float weight = 1.0f / (float)(sd.renderedFramesCount + 1u); /* :316 */
-            const float iw = 1.0f - weight;
-            acc = mk3(o.x * iw + result.x * weight, o.y * iw + result.y * weight, o.z * iw + result.z * weight);
-        }
-        store_pixel(image, wire, wire_ch, wm, W, lx, ly, acc); /* :323 */
-    }
+    if (!COUNT) accumulate_store(sd, image, wire, wire_ch, wm, W, lx, ly, old, result);
     if (COUNT) cnt.pixels++;
     phase_mark(cnt, 6);
 }
@@ -137,7 +157,7 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
 #endif
 /* A: the arithmetic mode (pt_device.h kArithExact / kArithFast, WCPT_OPTION_ARITH). A template parameter, so the fast
  * and the exact kernel of one configuration are two symbols; render builds only (launch_mega_render). */
-template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A>
+template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A, int STAGE>
 __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_scene_data sd, const wcpt_material* __restrict__ mats,
                                                     const wcpt_sphere* __restrict__ spheres,
                                                     const wcpt_draw_command* __restrict__ draws,
@@ -148,7 +168,8 @@ __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_sc
                                                     uint32_t scatter, const uint32_t* __restrict__ tile_order,
                                                     uint32_t* __restrict__ tile_cost, uint32_t* __restrict__ status,
                                                     unsigned long long* __restrict__ counters,
-                                                    uint32_t* __restrict__ prim_cache)
+                                                    uint32_t* __restrict__ prim_cache,
+                                                    const typename StageQueue<STAGE>::type q)
 {
     const uint64_t c0 = (!COUNT && tile_cost) ? __builtin_amdgcn_s_memtime() : 0ull;
     uint32_t tx, ty;
@@ -166,16 +187,16 @@ __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_sc
             uint64_t mem[kPrivateStack];
             PrivateStack<kPrivateStack> stk;
             stk.mem = (priv_u64_ptr)mem;
-            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE, PC, A>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
-                                            cnt, overflow, pcache);
+            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE, PC, A, STAGE>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
+                                            cnt, overflow, pcache, q);
         } else {
             __shared__ uint64_t s_stack[kLdsStack * 64];
             uint64_t spill[kSpillStack];
             LdsStack<kLdsStack, kSpillStack> stk;
             stk.base = (lds_u64_ptr)(s_stack + (threadIdx.x & 63u));
             stk.spill = (priv_u64_ptr)spill;
-            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE, PC, A>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
-                                            cnt, overflow, pcache);
+            shade_pixel<COUNT, DIAG, PAIRS, SINGLE, REUSE, PC, A, STAGE>(sd, mats, spheres, draws, tri_records, image, wire, wire_ch, W, H, rm, wm, lx, ly, stk,
+                                            cnt, overflow, pcache, q);
         }
     }
     if (overflow) atomicOr(status, 1u);
@@ -191,6 +212,49 @@ __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_sc
     if (!COUNT && (threadIdx.x & 63u) == 0u)
         for (int k = 0; k < kPhaseTimers; k++) atomicAdd(&counters[k], (unsigned long long)cnt.tim[k]);
 #endif
+}
+
+/* The tail of a split render (pt_device.h SplitQueue): wave b finishes the paths of queue entries [64 b, 64 b + 64), one
+ * per lane, and stores their pixels as the whole kernel does, gather payload included. The grid is the queue's
+ * capacity (the host never reads the count); a wave past the count exits at once. LDS stack, like its head. */
+template <bool PAIRS, bool SINGLE, int A>
+__global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_mk_tail(const wcpt_scene_data sd, const wcpt_material* __restrict__ mats,
+                                                 const wcpt_sphere* __restrict__ spheres,
+                                                 const wcpt_draw_command* __restrict__ draws,
+                                                 const uint64_t* __restrict__ tri_records, float4* __restrict__ image,
+                                                 float* __restrict__ wire, uint32_t wire_ch, uint32_t W, const RowMap wm,
+                                                 uint32_t* __restrict__ status, const SplitQueue q)
+{
+    /* the pipe's next frame counts in the other counter (no memset between frames): zeroed here, behind the previous
+     * frame's tail, which read it last, and before the next frame's head on the same stream */
+    if (blockIdx.x == 0u)
+        for (uint32_t s = threadIdx.x; s < kMkSplitSubQueues; s += 64u) q.count_next[s * kMkSplitCounterStride] = 0u;
+    /* entries [64 c, 64 c + 64) of sub-queue j (mk_split_rule.h) */
+    const uint32_t blocks = q.cap / 64u, j = blockIdx.x % kMkSplitSubQueues, c = blockIdx.x / kMkSplitSubQueues;
+    const uint32_t n = min(q.count[j * kMkSplitCounterStride], mk_split_sub_cap(blocks, j));
+    const uint32_t k = c * 64u + threadIdx.x;
+    const uint32_t i = mk_split_sub_first(blocks, j) + k;
+    if (k >= n || i >= q.cap) return;
+    PathState ps;
+    uint32_t rng, pixel;
+    split_load<A>(q, i, ps, rng, pixel);
+    const uint32_t lx = pixel % W, ly = pixel / W;
+    /* the accumulation read first, as in shade_pixel */
+    float4 old = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (sd.renderedFramesCount != 0) old = image[pixel];
+    __shared__ uint64_t s_stack[kLdsStack * 64];
+    uint64_t spill[kSpillStack];
+    LdsStack<kLdsStack, kSpillStack> stk;
+    stk.base = (lds_u64_ptr)(s_stack + (threadIdx.x & 63u));
+    stk.spill = (priv_u64_ptr)spill;
+    Counters cnt = {};
+    bool overflow = false;
+    /* shade_pixel's `result + TraceRay(...)` from a zero sum: the same addition, so a -0 radiance becomes +0 here too */
+    const f3 result = mk3(0.0f, 0.0f, 0.0f) +
+                      TraceTail<PAIRS, SINGLE, LdsStack<kLdsStack, kSpillStack>, A>(ps, rng, sd, mats, spheres, draws,
+                                                                                   tri_records, stk, cnt, overflow);
+    accumulate_store(sd, image, wire, wire_ch, wm, W, lx, ly, old, result);
+    if (overflow) atomicOr(status, 1u);
 }
 
 /* Derived triangle records (pt_device.h), single and pair formats: one thread per pair. Same subtractions as
@@ -559,10 +623,12 @@ hipError_t launch_build_primary_pairs(const void* pairs, uint32_t npairs, float 
 static_assert(dev::kPrimCacheNone == kPrimaryCacheNone && dev::kPrimCacheWrite == kPrimaryCacheWrite &&
                   dev::kPrimCacheRead == kPrimaryCacheRead, "primary-cache modes");
 static_assert(dev::kArithExact == WCPT_ARITH_EXACT && dev::kArithFast == WCPT_ARITH_FAST, "arithmetic modes");
+static_assert(dev::kSplitWords * 4u == kMkSplitEntryBytes, "split queue entry");
+/* q: the pipe's split queue for a head launch (STAGE), else unused */
 template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE = false, int PC = kPrimaryCacheNone,
-          int A = WCPT_ARITH_EXACT>
+          int A = WCPT_ARITH_EXACT, int STAGE = dev::kStageWhole>
 static hipError_t launch_mega(const LaunchArgs& a, MkState& mk, hipStream_t stream, uint32_t tilesX, uint32_t tiles,
-                              const uint32_t* list, uint32_t grid)
+                              const uint32_t* list, uint32_t grid, const dev::SplitQueue& q = dev::SplitQueue{})
 {
     /* scattered tile order: block b renders tile (b * m) mod tiles for an m coprime with tiles near 0.618 * tiles,
      * so the tiles resident on one CU at once come from all over the frame */
@@ -584,11 +650,13 @@ static hipError_t launch_mega(const LaunchArgs& a, MkState& mk, hipStream_t stre
     const bool cost_order = !COUNT && a.mk_tile_order == 2 && mk.cost != nullptr;
     const uint32_t* order = list ? list : (cost_order && mk.order_valid ? mk.order : nullptr);
     static_assert(!COUNT || A == WCPT_ARITH_EXACT, "the counting builds are exact");
-    hipLaunchKernelGGL((dev::pt_megakernel<COUNT, DIAG, SK, PAIRS, SINGLE, REUSE, PC, A>), dim3(list ? grid : tiles), dim3(64), 0,
+    typename dev::StageQueue<STAGE>::type qa;
+    if constexpr (STAGE == dev::kStageHead) qa = q;
+    hipLaunchKernelGGL((dev::pt_megakernel<COUNT, DIAG, SK, PAIRS, SINGLE, REUSE, PC, A, STAGE>), dim3(list ? grid : tiles), dim3(64), 0,
                        stream, a.sd, a.materials, a.spheres, a.draws, a.tri_records, a.image, a.wire, a.wire_ch, a.W, a.H,
                        RowMap{a.y0, a.row_shift, a.row_gap}, a.wire_rows, a.rows, tilesX, tiles, scatter, order,
                        cost_order ? mk.cost : nullptr, a.status, a.counters,
-                       PC != kPrimaryCacheNone ? static_cast<uint32_t*>(mk.prim_mem) : nullptr);
+                       PC != kPrimaryCacheNone ? static_cast<uint32_t*>(mk.prim_mem) : nullptr, qa);
     return hipGetLastError();
 }
 
@@ -614,6 +682,7 @@ void mk_release(MkState& mk)
     if (mk.fork) (void)hipEventDestroy(mk.fork);
     if (mk.mem) (void)hipFree(mk.mem);
     if (mk.prim_mem) (void)hipFree(mk.prim_mem);
+    if (mk.split_mem) (void)hipFree(mk.split_mem);
     const int cus = mk.cus;
     mk = MkState{};
     mk.cus = cus;
@@ -697,9 +766,27 @@ static hipError_t cost_order_sort(MkState& mk, uint32_t tiles, hipStream_t strea
 /* the render instantiations: sample reuse (samples > 1) x primary-cache mode of this render, in arithmetic mode A */
 template <int SK, bool PAIRS, bool SINGLE, int A>
 static hipError_t launch_mega_arith(const LaunchArgs& a, int pcmode, MkState& mk, hipStream_t stream, uint32_t tilesX,
-                                     uint32_t tiles, const uint32_t* list, uint32_t grid)
+                                     uint32_t tiles, const uint32_t* list, uint32_t grid, const dev::SplitQueue* q)
 {
     const bool reuse = a.sd.samples > 1u;
+    if constexpr (SK == 1) {
+        /* a split render (launch_megakernel: one sample, LDS stack): the head in this render's primary-cache mode, then
+         * the tail behind it on the same stream, one wave per 64 entries of the queue's capacity */
+        if (q != nullptr) {
+            constexpr int H = dev::kStageHead;
+            hipError_t e =
+                pcmode == kPrimaryCacheRead
+                    ? launch_mega<false, false, 1, PAIRS, SINGLE, false, kPrimaryCacheRead, A, H>(a, mk, stream, tilesX, tiles, list, grid, *q)
+                : pcmode == kPrimaryCacheWrite
+                    ? launch_mega<false, false, 1, PAIRS, SINGLE, false, kPrimaryCacheWrite, A, H>(a, mk, stream, tilesX, tiles, list, grid, *q)
+                    : launch_mega<false, false, 1, PAIRS, SINGLE, false, kPrimaryCacheNone, A, H>(a, mk, stream, tilesX, tiles, list, grid, *q);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((dev::pt_mk_tail<PAIRS, SINGLE, A>), dim3((q->cap + 63u) / 64u), dim3(64), 0, stream, a.sd,
+                               a.materials, a.spheres, a.draws, a.tri_records, a.image, a.wire, a.wire_ch, a.W, a.wire_rows,
+                               a.status, *q);
+            return hipGetLastError();
+        }
+    }
     if (pcmode == kPrimaryCacheRead) /* its one-sample form holds the sample count as a constant: only for samples == 1 */
         return a.sd.samples != 1u
                    ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheRead, A>(a, mk, stream, tilesX, tiles, list, grid)
@@ -715,25 +802,26 @@ static hipError_t launch_mega_arith(const LaunchArgs& a, int pcmode, MkState& mk
  * have none (launch_mega_sk) */
 template <int SK, bool PAIRS, bool SINGLE>
 static hipError_t launch_mega_render(const LaunchArgs& a, int pcmode, MkState& mk, hipStream_t stream, uint32_t tilesX,
-                                     uint32_t tiles, const uint32_t* list, uint32_t grid)
+                                     uint32_t tiles, const uint32_t* list, uint32_t grid, const dev::SplitQueue* q)
 {
     return a.arith == WCPT_ARITH_FAST
-               ? launch_mega_arith<SK, PAIRS, SINGLE, WCPT_ARITH_FAST>(a, pcmode, mk, stream, tilesX, tiles, list, grid)
-               : launch_mega_arith<SK, PAIRS, SINGLE, WCPT_ARITH_EXACT>(a, pcmode, mk, stream, tilesX, tiles, list, grid);
+               ? launch_mega_arith<SK, PAIRS, SINGLE, WCPT_ARITH_FAST>(a, pcmode, mk, stream, tilesX, tiles, list, grid, q)
+               : launch_mega_arith<SK, PAIRS, SINGLE, WCPT_ARITH_EXACT>(a, pcmode, mk, stream, tilesX, tiles, list, grid, q);
 }
 
 /* pcmode: the render's primary-cache mode (the COUNT / DIAG builds never read or write the cache: their counters are
  * the reference's) */
 template <bool PAIRS, bool SINGLE>
 static hipError_t launch_mega_sk(const LaunchArgs& a, int mode, int stack_kind, int pcmode, MkState& mk, hipStream_t stream,
-                                 uint32_t tilesX, uint32_t tiles, const uint32_t* list = nullptr, uint32_t grid = 0)
+                                 uint32_t tilesX, uint32_t tiles, const uint32_t* list = nullptr, uint32_t grid = 0,
+                                 const dev::SplitQueue* q = nullptr)
 {
     if (stack_kind == 0) {
-        if (mode == kModeRender) return launch_mega_render<0, PAIRS, SINGLE>(a, pcmode, mk, stream, tilesX, tiles, list, grid);
+        if (mode == kModeRender) return launch_mega_render<0, PAIRS, SINGLE>(a, pcmode, mk, stream, tilesX, tiles, list, grid, nullptr);
         if (mode == kModeCount) return launch_mega<true, false, 0, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
         return launch_mega<true, true, 0, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
     }
-    if (mode == kModeRender) return launch_mega_render<1, PAIRS, SINGLE>(a, pcmode, mk, stream, tilesX, tiles, list, grid);
+    if (mode == kModeRender) return launch_mega_render<1, PAIRS, SINGLE>(a, pcmode, mk, stream, tilesX, tiles, list, grid, q);
     if (mode == kModeCount) return launch_mega<true, false, 1, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
     return launch_mega<true, true, 1, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
 }
@@ -824,12 +912,48 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
             mk.prim_bytes = bytes;
         }
     }
-    auto launch = [&](const LaunchArgs& la, hipStream_t s, const uint32_t* list, uint32_t grid) {
-        if (la.pair_records)
-            return single ? launch_mega_sk<true, true>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid)
-                          : launch_mega_sk<true, false>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid);
-        return single ? launch_mega_sk<false, true>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid)
-                      : launch_mega_sk<false, false>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid);
+    /* Split render (mk_split_rule.h has the rule and the queues' layout): head and tail go onto the pipe's stream one
+     * after the other, so whatever orders the pipes' frames -- the image's read-modify-write, the primary cache, every
+     * join -- orders them as it orders whole launches; a pixel's frames still accumulate in stream order, whichever
+     * stage stores it. The tile costs become the head's times (the tail has no tiles). */
+    const uint32_t cut = mk_split_cut(a.mk_split, mode == kModeRender && stack_kind == 1, a.sd.samples,
+                                      a.sd.maxBounceCount, tiles, 16ull * (uint64_t)mk.cus, a.triangles);
+    const MkSplitLayout lay = mk_split_layout(tiles, pipes);
+    if (cut != 0u && lay.entries > mk.split_entries) { /* grows like mk.prim_mem; first: both counters of each pipe zero */
+        e = mk_join(mk, stream);
+        if (e == hipSuccess && mk.split_mem) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) return e;
+        if (mk.split_mem) (void)hipFree(mk.split_mem);
+        mk.split_mem = nullptr;
+        mk.split_entries = 0;
+        const size_t state_bytes = (size_t)lay.entries * kMkSplitEntryBytes;
+        const size_t ctr_bytes = 2u * kMkPipes * kMkSplitCounterWords * sizeof(uint32_t);
+        e = hipMalloc(&mk.split_mem, state_bytes + ctr_bytes);
+        if (e != hipSuccess) return e;
+        mk.split_ctr = reinterpret_cast<uint32_t*>(static_cast<char*>(mk.split_mem) + state_bytes);
+        mk.split_parity[0] = mk.split_parity[1] = 0u;
+        e = hipMemsetAsync(mk.split_ctr, 0, ctr_bytes, stream);
+        if (e != hipSuccess) return e;
+        mk.split_entries = lay.entries;
+    }
+    auto launch = [&](const LaunchArgs& la, hipStream_t s, const uint32_t* list, uint32_t grid, uint32_t p) {
+        dev::SplitQueue q = {};
+        if (cut != 0u) { /* pipe p's queue and this frame's counter; the pipe's next frame takes the other */
+            q.state = static_cast<uint32_t*>(mk.split_mem) + (size_t)dev::kSplitWords * lay.first[p];
+            q.count = mk.split_ctr + (size_t)(2u * p + mk.split_parity[p]) * kMkSplitCounterWords;
+            q.count_next = mk.split_ctr + (size_t)(2u * p + (mk.split_parity[p] ^ 1u)) * kMkSplitCounterWords;
+            q.cap = lay.cap[p];
+            q.cut = cut;
+        }
+        const dev::SplitQueue* qp = cut != 0u ? &q : nullptr;
+        const hipError_t le =
+            la.pair_records
+                ? (single ? launch_mega_sk<true, true>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid, qp)
+                          : launch_mega_sk<true, false>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid, qp))
+                : (single ? launch_mega_sk<false, true>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid, qp)
+                          : launch_mega_sk<false, false>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid, qp));
+        if (le == hipSuccess && cut != 0u) mk.split_parity[p] ^= 1u;
+        return le;
     };
     if (pipes) {
         if (!mk.pending) { /* fork: pipe 1 after everything queued on the context's stream */
@@ -843,7 +967,7 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
             if (e != hipSuccess) return e;
         }
         const uint32_t half = (tiles + 1u) / 2u;
-        e = launch(a, stream, mk.split, half);
+        e = launch(a, stream, mk.split, half, 0u);
         /* pending from the first enqueue on: a failed second launch still leaves the first to join */
         mk.pending = true;
         mk.pending_tiles = tiles;
@@ -851,11 +975,12 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
         if (e == hipSuccess) {
             LaunchArgs a1 = a;
             if (a.tri_records_pipe1) a1.tri_records = a.tri_records_pipe1;
-            e = launch(a1, mk.pipe[1], mk.split + half, tiles - half);
+            e = launch(a1, mk.pipe[1], mk.split + half, tiles - half, 1u);
         }
     } else {
-        e = launch(a, stream, nullptr, 0);
+        e = launch(a, stream, nullptr, 0, 0u);
     }
+    if (e == hipSuccess && cut != 0u) mk.split_renders++;
     if (e == hipSuccess && pcmode == kPrimaryCacheWrite) {
         mk.prim_key = *a.prim_key;
         mk.prim_valid = true;

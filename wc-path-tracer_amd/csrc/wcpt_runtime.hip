@@ -160,6 +160,7 @@ struct wcpt_context {
     int wf_stack = 10;                 /* WCPT_OPTION_WF_STACK: LDS stack entries of the wavefront trace kernel */
     int tri_cache = 1;                 /* WCPT_OPTION_TRIANGLE_CACHE */
     int prim_cache = 1;                /* WCPT_OPTION_PRIMARY_CACHE (active only with tri_cache) */
+    int mk_split = wcpt::kMkSplitAuto; /* WCPT_OPTION_MK_SPLIT */
     int packed_refs = 1;               /* WCPT_OPTION_PACKED_REFS */
     int wf_fetch = -1;                 /* WCPT_OPTION_WF_FETCH */
     int wf_persist = -1;               /* WCPT_OPTION_WF_PERSIST */
@@ -190,6 +191,7 @@ struct wcpt_context {
         uint32_t n = 0;
         uint32_t origin[3] = {0, 0, 0};
         bool pair_records = false, wf_fast = false;
+        uint64_t triangles = 0; /* of all draws (LaunchArgs::triangles) */
         int kernel_run = WCPT_KERNEL_MEGAKERNEL;
     } prep;
     struct ValidCache {
@@ -385,6 +387,7 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
         std::memcmp(pc.origin, sd.position, sizeof(pc.origin)) == 0) {
         a.pair_records = pc.pair_records;
         a.wf_fast = pc.wf_fast;
+        a.triangles = pc.triangles;
         ctx->kernel_run = pc.kernel_run;
         a.tri_records = ctx->d_tri_table;
         set_pipe1_records(ctx, n, a);
@@ -412,6 +415,7 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
         std::memcpy(pc.origin, origin, sizeof(pc.origin));
         a.pair_records = pc.pair_records;
         a.wf_fast = pc.wf_fast;
+        a.triangles = pc.triangles;
         ctx->kernel_run = pc.kernel_run;
         a.tri_records = ctx->d_tri_table;
         set_pipe1_records(ctx, n, a);
@@ -539,6 +543,7 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
         tris_max = std::max<uint64_t>(tris_max, ntri);
         leaves_all += bb ? (bb->bytes / sizeof(wcpt_node) + 1u) / 2u : ntri; /* unknown BVH: assume thin leaves */
     }
+    a.triangles = tris_all;
     /* the wavefront trace's one-draw fast layout: packed stack refs, 24-bit record offsets, buffer-resource node loads */
     a.wf_fast = n == 1 && (ctx->tri_table[3] & 15u) == 15u && (ctx->tri_table[2] >> 32) > 0;
     /* pair leaves address a draw's pair records with 32-bit byte offsets (pt_device.h load_pair_at) */
@@ -623,6 +628,7 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
         std::memcpy(pc.origin, sd.position, sizeof(pc.origin));
         pc.pair_records = a.pair_records;
         pc.wf_fast = a.wf_fast;
+        pc.triangles = a.triangles;
         pc.kernel_run = ctx->kernel_run;
     }
     return WCPT_SUCCESS;
@@ -735,6 +741,7 @@ int render_common(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t mate
      * WCPT_KERNEL_AUTO's choice), the counting and the diagnostics runs are exact */
     a.arith = (mode == wcpt::kModeRender && ctx->kernel_run == WCPT_KERNEL_MEGAKERNEL) ? ctx->arith : WCPT_ARITH_EXACT;
     ctx->arith_run = a.arith;
+    a.mk_split = ctx->mk_split;
     /* the other kernel's pending frames (the same image) first */
     if (ctx->kernel_run != WCPT_KERNEL_MEGAKERNEL && ctx->mk.pending)
         HIP_TRY(ctx, wcpt::mk_join(ctx->mk, ctx->stream), "frame overlap join");
@@ -1096,6 +1103,11 @@ int wcpt_set_option(wcpt_context* ctx, int option, int value)
         ctx->prim_cache = value;
         ctx->generation++;
         return WCPT_SUCCESS;
+    case WCPT_OPTION_MK_SPLIT:
+        if (value < wcpt::kMkSplitAuto || value > wcpt::kMkSplitMaxCut)
+            return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "megakernel split %d", value);
+        ctx->mk_split = value;
+        return WCPT_SUCCESS;
     case WCPT_OPTION_ARITH:
         if (value != WCPT_ARITH_EXACT && value != WCPT_ARITH_FAST)
             return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "arithmetic mode %d", value);
@@ -1437,6 +1449,13 @@ int wcpt_primary_cache_stats(wcpt_context* ctx, uint64_t* writes, uint64_t* read
     if (!ctx) return set_error(nullptr, WCPT_ERROR_INVALID_HANDLE, "null context");
     if (writes) *writes = ctx->mk.prim_writes;
     if (reads) *reads = ctx->mk.prim_reads;
+    return WCPT_SUCCESS;
+}
+
+int wcpt_mk_split_stats(wcpt_context* ctx, uint64_t* renders)
+{
+    if (!ctx) return set_error(nullptr, WCPT_ERROR_INVALID_HANDLE, "null context");
+    if (renders) *renders = ctx->mk.split_renders;
     return WCPT_SUCCESS;
 }
 

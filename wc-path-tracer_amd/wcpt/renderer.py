@@ -169,6 +169,12 @@ class Context:
         self._chk(lib.wcpt_primary_cache_stats(self.h, C.byref(w), C.byref(r)))
         return int(w.value), int(r.value)
 
+    def mk_split_stats(self) -> int:
+        """The renders that ran as a head and a tail launch (WCPT_OPTION_MK_SPLIT)."""
+        n = C.c_uint64(0)
+        self._chk(lib.wcpt_mk_split_stats(self.h, C.byref(n)))
+        return int(n.value)
+
     def render_counters(self, sd: np.ndarray, materials: int, spheres: int, draws: int,
                         diagnostics: bool = False) -> dict:
         """Reference-algorithm work counters of one frame (COUNTER_FIELDS); with diagnostics=True also the
