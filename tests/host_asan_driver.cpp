@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../include/wcpt.h"
+#include "../wc-path-tracer_amd/csrc/mk_variant.h"
 
 static int failures = 0;
 #define CHECK(cond)                                                         \
@@ -187,6 +188,24 @@ int main(int argc, char** argv)
         }
         wcpt_scene_free(&s);
     }
+
+    /* 5. the megakernel's variant selection (mk_variant.h, host only): every selection over its inputs' cross product,
+     * out-of-range ones included, is built, and its number indexes the dispatcher's table */
+    for (int mode = -1; mode <= 3; mode++)
+        for (int stack = -1; stack <= 2; stack++)
+            for (uint32_t draws = 0; draws <= 2; draws++)
+                for (uint32_t samples : {0u, 1u, 2u, 16u, 0xFFFFFFFFu})
+                    for (int pc = -1; pc <= 3; pc++)
+                        for (int arith = -1; arith <= 2; arith++)
+                            for (int k = 0; k < 4; k++) {
+                                const wcpt::MkSelection s = wcpt::mk_variant_select(mode, stack, (k & 1) != 0, draws,
+                                                                                     samples, pc, arith, (k & 2) != 0);
+                                CHECK(s.n == 1u || s.n == 2u);
+                                for (uint32_t i = 0; i < s.n; i++) {
+                                    CHECK(wcpt::mk_variant_built(s.v[i]));
+                                    CHECK(wcpt::mk_variant_code(s.v[i]) < wcpt::kMkVariantCodes);
+                                }
+                            }
     std::printf("host sanitizer driver: %d failed checks\n", failures);
     return failures ? 1 : 0;
 }

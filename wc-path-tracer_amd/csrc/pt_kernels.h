@@ -7,6 +7,7 @@
 
 #include "../../include/wcpt.h"
 #include "mk_split_rule.h"
+#include "mk_variant.h"
 #include "primary_cache_key.h"
 #include "row_map.h"
 
@@ -193,9 +194,7 @@ constexpr int kMaxFrameStreams = 4;
 int context_frame_streams(wcpt_context* ctx, hipStream_t* out, int cap);
 hipError_t mk_join(MkState& mk, hipStream_t stream);
 
-/* Launch modes: render the frame; count the reference algorithm's work (no image write); count + SIMD
- * diagnostics (ballot-based step counters, tools/diag.py). */
-constexpr int kModeRender = 0, kModeCount = 1, kModeDiag = 2;
+/* Launch modes (kModeRender / kModeCount / kModeDiag): mk_variant.h */
 
 /* Derived triangle records (pt_device.h): triangle k = index positions 3k..3k+2 stored as (a, b - a, c - a);
  * singles: 48 B per triangle; pairs: 80 B per triangle pair (2j, 2j+1). */

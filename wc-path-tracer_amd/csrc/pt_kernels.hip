@@ -10,9 +10,13 @@
  * __ballot inside the traversal loop (tools/diag.py only — kept out of the COUNT build the parity tests use).
  * The render builds come in three primary-cache modes (PC; pt_device.h intersect, primary_cache_key.h): none, write
  * (stores each pixel's primary Intersect record) and read (resolves the primary segment from it).
+ * mk_variant.h is the list of the instances: 96 render, 24 head (the first launch of a split render) and 16 counting
+ * instances of pt_megakernel and 8 of pt_mk_tail; the dispatcher below (mk_dispatch) instantiates exactly those.
  */
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+
+#include <utility>
 
 #include "pt_device.h"
 #include "pt_kernels.h"
@@ -115,7 +119,7 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
         prim_rec.y = __uint_as_float(pl[1]);
         if (!SINGLE) prim_rec.z = __uint_as_float(pl[2]);
     }
-    /* the one-sample read build (launch_mega_render) has its sample count as a constant: the record then dies at its one
+    /* the one-sample read build (mk_variant.h mk_variant_select) has its sample count as a constant: the record then dies at its one
      * use instead of staying live across a sample loop (intersect: 20 VGPRs) */
     /* so has a head launch (STAGE; the runtime splits one-sample renders only) */
     const uint32_t samples = ((PC == kPrimCacheRead && !REUSE) || STAGE == kStageHead) ? 1u : sd.samples;
@@ -156,7 +160,9 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
 #define WCPT_MK_WAVES 1
 #endif
 /* A: the arithmetic mode (pt_device.h kArithExact / kArithFast, WCPT_OPTION_ARITH). A template parameter, so the fast
- * and the exact kernel of one configuration are two symbols; render builds only (launch_mega_render). */
+ * and the exact kernel of one configuration are two symbols; render builds only.
+ * The nine template parameters are the fields of an MkVariant: mk_variant.h states which combinations are instantiated
+ * (mk_variant_built: 136 of this kernel and 8 of pt_mk_tail per code object) and which one a launch takes. */
 template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A, int STAGE>
 __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_scene_data sd, const wcpt_material* __restrict__ mats,
                                                     const wcpt_sphere* __restrict__ spheres,
@@ -345,245 +351,6 @@ __global__ __launch_bounds__(256) void build_primary_pairs(const float4* __restr
     o[6] = make_float4(t[0][6], t[1][6], 0.0f, 0.0f);       /* tq */
 }
 
-/* Device self-tests: evaluate the device definitions of the RNG and the deterministic libm on host inputs. */
-__global__ __launch_bounds__(256) void pt_selftest(int fn, const uint32_t* __restrict__ in, const uint32_t* __restrict__ in2,
-                                                   uint32_t* __restrict__ out, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t a = in[i];
-    switch (fn) {
-    case 0: out[i] = pcg_hash(a); break;
-    case 1: {
-        uint32_t s = a;
-        for (int k = 0; k < 4; k++) out[4u * i + (uint32_t)k] = __float_as_uint(rand_f(s));
-        break;
-    }
-    case 2: out[i] = __float_as_uint(wcpt_logf(__uint_as_float(a))); break;
-    case 3: out[i] = __float_as_uint(wcpt_cosf(__uint_as_float(a))); break;
-    case 4: out[i] = __float_as_uint(wcpt_expf(__uint_as_float(a))); break;
-    case 5: out[i] = __float_as_uint(sqrt_exact(__uint_as_float(a))); break;
-    case 6: out[i] = __float_as_uint(__uint_as_float(a) / __uint_as_float(in2[i])); break;
-    case 8: { /* exhaustive fast-reciprocal check: mismatches of rcp_exact's fast path vs IEEE 1/x over the 2^16
-                 inputs (a << 16) | k inside the fast path's range */
-        uint32_t bad = 0;
-        for (uint32_t k = 0; k < 65536u; k++) {
-            const float x = __uint_as_float((a << 16) | k);
-            const float ax = fabsf(x);
-            if (!(ax >= 0x1p-126f && ax < 0x1p126f)) continue;
-            const float y = __builtin_amdgcn_rcpf(x);
-            const float e = __builtin_fmaf(-x, y, 1.0f);
-            const float r = __builtin_fmaf(e, y, y);
-            bad += (__float_as_uint(r) != __float_as_uint(1.0f / x)) ? 1u : 0u;
-        }
-        out[i] = bad;
-        break;
-    }
-    case 9: out[i] = __float_as_uint(rcp_exact(__uint_as_float(a))); break;
-    case 10:   /* as 8, over every normal binary32 input (v_cmp_class range test) */
-    case 11: { /* as 8, over every input (no range test) */
-        uint32_t bad = 0;
-        for (uint32_t k = 0; k < 65536u; k++) {
-            const float x = __uint_as_float((a << 16) | k);
-            if (fn == 10 && !__builtin_isnormal(x)) continue;
-            const float y = __builtin_amdgcn_rcpf(x);
-            const float e = __builtin_fmaf(-x, y, 1.0f);
-            const float r = __builtin_fmaf(e, y, y);
-            const float q = 1.0f / x;
-            bad += (__float_as_uint(r) != __float_as_uint(q) && !(r != r && q != q)) ? 1u : 0u;
-        }
-        out[i] = bad;
-        break;
-    }
-    case 12: { /* the kernels' reciprocals vs the IEEE quotient over the 2^16 inputs x = (a << 16) | k: rcp_exact(x), and
-                  rcp2_exact on the pair (x, ~x) (every bit pattern in both halves); mismatches, NaN == NaN */
-        uint32_t bad = 0;
-        for (uint32_t k = 0; k < 65536u; k++) {
-            const uint32_t bits = (a << 16) | k;
-            const float x = __uint_as_float(bits), x2 = __uint_as_float(~bits);
-            const float r = rcp_exact(x);
-            v2f xx;
-            xx.x = x;
-            xx.y = x2;
-            const v2f rr = rcp2_exact(xx);
-            const float q = 1.0f / x, q2 = 1.0f / x2;
-            bad += (__float_as_uint(r) != __float_as_uint(q) && !(r != r && q != q)) ? 1u : 0u;
-            bad += (__float_as_uint(rr.x) != __float_as_uint(q) && !(rr.x != rr.x && q != q)) ? 1u : 0u;
-            bad += (__float_as_uint(rr.y) != __float_as_uint(q2) && !(rr.y != rr.y && q2 != q2)) ? 1u : 0u;
-        }
-        out[i] = bad;
-        break;
-    }
-    case 13: { /* how many of the 2^16 inputs (a << 16) | k fail the fast result's class check (general division) */
-        uint32_t slow = 0;
-        for (uint32_t k = 0; k < 65536u; k++)
-            slow += rcp_fast_ok(rcp_fast_raw(__uint_as_float((a << 16) | k))) ? 0u : 1u;
-        out[i] = slow;
-        break;
-    }
-    case 14: { /* acceptance tests on (u, v) = (in, in2) with t = 1: bit 0 = accept_tri, bit 1 = accept_tri_w */
-        const float u = __uint_as_float(a), v = __uint_as_float(in2[i]);
-        const float uv = u + v;
-        out[i] = (accept_tri(1.0f, u, v, uv) ? 1u : 0u) | (accept_tri_w(1.0f, u, v, 1.0f - uv) ? 2u : 0u);
-        break;
-    }
-    case 15: { /* the kernels' sqrt (sqrt_exact) vs hipcc's correctly rounded sqrtf over the 2^16 inputs (a << 16) | k:
-                  mismatches, NaN == NaN */
-        uint32_t bad = 0;
-        for (uint32_t k = 0; k < 65536u; k++) {
-            const float x = __uint_as_float((a << 16) | k);
-            const float r = sqrt_exact(x), q = sqrtf(x);
-            bad += (__float_as_uint(r) != __float_as_uint(q) && !(r != r && q != q)) ? 1u : 0u;
-        }
-        out[i] = bad;
-        break;
-    }
-    case 17: { /* the take's two forms (pt_device.h take_bits) over t = (a << 16) | k, k < 2^16, for rec.t = in2: mismatches
-                  between (t > 0 && t < rec.t) and bits(t) - 1 < bits(rec.t) - 1 */
-        const float rt = __uint_as_float(in2[i]);
-        const uint32_t rb = take_bits(rt);
-        uint32_t bad = 0;
-        for (uint32_t k = 0; k < 65536u; k++) {
-            const float t = __uint_as_float((a << 16) | k);
-            bad += ((t > 0.0f && t < rt) != (take_bits(t) < rb)) ? 1u : 0u;
-        }
-        out[i] = bad;
-        break;
-    }
-    case 16: { /* GLSL vector / scalar as the kernels evaluate it (pt_device.h operator/): in * RN(1 / in2) */
-        const f3 q = mk3(__uint_as_float(a), 0.0f, 0.0f) / __uint_as_float(in2[i]);
-        out[i] = __float_as_uint(q.x);
-        break;
-    }
-    case 7: { /* RandomDirection: 3 words per input */
-        uint32_t s = a;
-        const f3 d = RandomDirection(s);
-        out[3u * i + 0u] = __float_as_uint(d.x);
-        out[3u * i + 1u] = __float_as_uint(d.y);
-        out[3u * i + 2u] = __float_as_uint(d.z);
-        break;
-    }
-    /* the fast arithmetic mode's device functions (pt_device.h kArithFast), mirroring fn 2, 3, 5, 9 and 7 */
-    case 18: out[i] = __float_as_uint(log_fast(__uint_as_float(a))); break;
-    case 19: out[i] = __float_as_uint(cos2pi_fast(__uint_as_float(a))); break; /* cos(2 pi u) given u */
-    case 20: out[i] = __float_as_uint(sqrt_a<kArithFast>(__uint_as_float(a))); break;
-    case 21: out[i] = __float_as_uint(rcp_a<kArithFast>(__uint_as_float(a))); break;
-    case 22: { /* fast RandomDirection: 3 words per input */
-        uint32_t s = a;
-        const f3 d = RandomDirection<kArithFast>(s);
-        out[3u * i + 0u] = __float_as_uint(d.x);
-        out[3u * i + 1u] = __float_as_uint(d.y);
-        out[3u * i + 2u] = __float_as_uint(d.z);
-        break;
-    }
-    default: break;
-    }
-}
-
-/* Geometry self-tests: the composite device functions of the render kernels, called as those kernels call them, in the
- * arithmetic mode A (wcpt.h wcpt_selftest_geometry lists the fn numbers and the words of an item). The runtime checks
- * fn, in_words and out_words, so item i owns in[i * in_words ..) and out[i * out_words ..). One kernel per function
- * and mode: each is a few dozen instructions (and hipcc 7.2's register allocator crashes on all of them in one switch). */
-template <int A, int FN>
-__global__ __launch_bounds__(256) void pt_selftest_geometry(const uint32_t* __restrict__ in, uint32_t in_words,
-                                                            uint32_t* __restrict__ out, uint32_t out_words, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t* x = in + (uint64_t)i * in_words;
-    uint32_t* y = out + (uint64_t)i * out_words;
-    auto f = [&](uint32_t k) { return __uint_as_float(x[k]); };
-    auto v3 = [&](uint32_t k) { return mk3(f(k), f(k + 1u), f(k + 2u)); };
-    auto put = [&](uint32_t k, float v) { y[k] = __float_as_uint(v); };
-    auto put3 = [&](uint32_t k, f3 v) { put(k, v.x); put(k + 1u, v.y); put(k + 2u, v.z); };
-    Ray r; /* fn 0..4 and 7 start with origin, direction (fn 5 and 6 have fewer words: nothing else is read for them) */
-    if constexpr (FN <= 4 || FN == 7) {
-        r.origin = v3(0);
-        r.direction = v3(3);
-        r.invDirection = rcp3_a<A>(r.direction);
-    }
-    if constexpr (FN == 0) { /* origin, direction, a, b, c */
-        const f3 a = v3(6), b = v3(9), c = v3(12);
-        put(0, rayTriangleE<A>(r, a, b - a, c - a));
-    } else if constexpr (FN == 1 || FN == 2) { /* origin, direction, then (a, e1, e2) of the pair's two triangles */
-        TriPair p;
-        p.ax = v2f{f(6), f(15)};   p.ay = v2f{f(7), f(16)};   p.az = v2f{f(8), f(17)};
-        p.e1x = v2f{f(9), f(18)};  p.e1y = v2f{f(10), f(19)}; p.e1z = v2f{f(11), f(20)};
-        p.e2x = v2f{f(12), f(21)}; p.e2y = v2f{f(13), f(22)}; p.e2z = v2f{f(14), f(23)};
-        PairHit h;
-        if constexpr (FN == 1) {
-            h = rayTrianglePair<A>(r, p);
-        } else { /* the primary-ray record of this origin, as build_primary_pairs derives it */
-            float t0[7], t1[7];
-            primary_terms(r.origin.x, r.origin.y, r.origin.z, p.ax.x, p.ay.x, p.az.x, p.e1x.x, p.e1y.x, p.e1z.x, p.e2x.x,
-                          p.e2y.x, p.e2z.x, t0);
-            primary_terms(r.origin.x, r.origin.y, r.origin.z, p.ax.y, p.ay.y, p.az.y, p.e1x.y, p.e1y.y, p.e1z.y, p.e2x.y,
-                          p.e2y.y, p.e2z.y, t1);
-            TriPairP q;
-            q.e1x = p.e1x; q.e1y = p.e1y; q.e1z = p.e1z;
-            q.e2x = p.e2x; q.e2y = p.e2y; q.e2z = p.e2z;
-            q.oax = v2f{t0[0], t1[0]}; q.oay = v2f{t0[1], t1[1]}; q.oaz = v2f{t0[2], t1[2]};
-            q.qx = v2f{t0[3], t1[3]};  q.qy = v2f{t0[4], t1[4]};  q.qz = v2f{t0[5], t1[5]};
-            q.tq = v2f{t0[6], t1[6]};
-            h = rayTrianglePairP<A>(r, q);
-        }
-        put(0, h.t.x);
-        put(1, h.t.y);
-        y[2] = h.hit0 ? 1u : 0u;
-        y[3] = h.hit1 ? 1u : 0u;
-    } else if constexpr (FN == 3) { /* origin, direction, centre, radius */
-        put(0, raySphereNear<A>(r, v3(6), f(9)));
-    } else if constexpr (FN == 4) { /* origin, direction, t, centre, radius: the hit epilogue of a sphere */
-        wcpt_sphere s;
-        s.position[0] = f(7); s.position[1] = f(8); s.position[2] = f(9);
-        s.radius = f(10);
-        s.material = 0u;
-        const Hit h = resolve_hit<kShadeA<A>>(r, f(6), kSpherePrim, 0u, &s, nullptr, nullptr);
-        put3(0, h.p);
-        put3(3, h.normal);
-        y[6] = h.front ? 1u : 0u;
-    } else if constexpr (FN == 5) { /* direction, normal, iorA, iorB: the optics of path_shade's dielectric branch */
-        constexpr int S = kShadeA<A>;
-        const f3 d = v3(0), nrm = v3(3);
-        const float iorA = f(6), iorB = f(7);
-        put3(0, reflect_a<S>(d, nrm));
-        put3(3, refract_a<S>(d, nrm, div_a<S>(iorA, iorB)));
-        put(6, CalculateReflectance<S>(d, nrm, iorA, iorB));
-    } else if constexpr (FN == 6) { /* a 3-vector: normalize and the component reciprocals (path_shade's new direction) */
-        constexpr int S = kShadeA<A>;
-        put3(0, normalize_a<S>(v3(0)));
-        put3(3, rcp3_a<S>(v3(0)));
-    } else if constexpr (FN == 7) { /* origin, direction, Hit p, normal, t, front, one material (15 words), rng state,
-                                       transmittance: one path_shade step that is neither the last segment nor a miss */
-        static_assert(sizeof(wcpt_material) == 60, "15 words");
-        uint32_t mw[15];
-        for (uint32_t k = 0; k < 15u; k++) mw[k] = x[14u + k];
-        wcpt_material m;
-        __builtin_memcpy(&m, mw, sizeof(m));
-        PathState ps;
-        ps.ray = r;
-        ps.totalLight = mk3(0.0f, 0.0f, 0.0f);
-        ps.transmittance = v3(30);
-        ps.bounce = 0;
-        Hit h;
-        h.p = v3(6);
-        h.normal = v3(9);
-        h.t = f(12);
-        h.front = x[13] != 0u;
-        h.hit = true;
-        h.material = 0;
-        wcpt_scene_data sd = {};
-        sd.maxBounceCount = 1000u;
-        uint32_t rng = x[29];
-        f3 L;
-        (void)path_shade<kShadeA<A>>(ps, h, rng, sd, &m, L, false);
-        put3(0, ps.ray.origin);
-        put3(3, ps.ray.direction);
-        put3(6, ps.transmittance);
-        y[9] = rng;
-    }
-}
-
 } // namespace dev
 
 /* ------------------------------------------------------------------------------------------------ */
@@ -618,18 +385,30 @@ hipError_t launch_build_primary_pairs(const void* pairs, uint32_t npairs, float 
     return hipGetLastError();
 }
 
-/* list / grid: a frame-overlap pipe's share of the cost-ordered tiles (MkState::split); null: every tile, in the order
- * below */
 static_assert(dev::kPrimCacheNone == kPrimaryCacheNone && dev::kPrimCacheWrite == kPrimaryCacheWrite &&
                   dev::kPrimCacheRead == kPrimaryCacheRead, "primary-cache modes");
 static_assert(dev::kArithExact == WCPT_ARITH_EXACT && dev::kArithFast == WCPT_ARITH_FAST, "arithmetic modes");
 static_assert(dev::kSplitWords * 4u == kMkSplitEntryBytes, "split queue entry");
-/* q: the pipe's split queue for a head launch (STAGE), else unused */
-template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE = false, int PC = kPrimaryCacheNone,
-          int A = WCPT_ARITH_EXACT, int STAGE = dev::kStageWhole>
-static hipError_t launch_mega(const LaunchArgs& a, MkState& mk, hipStream_t stream, uint32_t tilesX, uint32_t tiles,
-                              const uint32_t* list, uint32_t grid, const dev::SplitQueue& q = dev::SplitQueue{})
+static_assert(dev::kStageWhole == kMkStageWhole && dev::kStageHead == kMkStageHead && dev::kStageTail == kMkStageTail,
+              "launch stages");
+/* One launch of launch_megakernel: the frame's arguments, the stream (the context's or a pipe's), its share of the
+ * cost-ordered tiles (list / grid; null: every tile, in the order below) and, for a split render, the pipe's queue. */
+struct MkLaunch {
+    const LaunchArgs& a;
+    MkState& mk;
+    hipStream_t stream;
+    uint32_t tilesX, tiles;
+    const uint32_t* list;
+    uint32_t grid;
+    dev::SplitQueue q;
+};
+
+template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A, int STAGE>
+static hipError_t launch_mega(const MkLaunch& l)
 {
+    const LaunchArgs& a = l.a;
+    MkState& mk = l.mk;
+    const uint32_t tiles = l.tiles;
     /* scattered tile order: block b renders tile (b * m) mod tiles for an m coprime with tiles near 0.618 * tiles,
      * so the tiles resident on one CU at once come from all over the frame */
     /* 3, 4, 5, 6: striped XCD bands of 1, 2, 4, 8 tile rows (tile_of_block: even scatter = 2 x stripe height);
@@ -648,16 +427,48 @@ static hipError_t launch_mega(const LaunchArgs& a, MkState& mk, hipStream_t stre
     /* cost-ordered tiles (auto order, render launches): this render records every tile's time, and the renders after
      * a sort (launch_megakernel) take the tiles longest first */
     const bool cost_order = !COUNT && a.mk_tile_order == 2 && mk.cost != nullptr;
-    const uint32_t* order = list ? list : (cost_order && mk.order_valid ? mk.order : nullptr);
-    static_assert(!COUNT || A == WCPT_ARITH_EXACT, "the counting builds are exact");
-    typename dev::StageQueue<STAGE>::type qa;
-    if constexpr (STAGE == dev::kStageHead) qa = q;
-    hipLaunchKernelGGL((dev::pt_megakernel<COUNT, DIAG, SK, PAIRS, SINGLE, REUSE, PC, A, STAGE>), dim3(list ? grid : tiles), dim3(64), 0,
-                       stream, a.sd, a.materials, a.spheres, a.draws, a.tri_records, a.image, a.wire, a.wire_ch, a.W, a.H,
-                       RowMap{a.y0, a.row_shift, a.row_gap}, a.wire_rows, a.rows, tilesX, tiles, scatter, order,
-                       cost_order ? mk.cost : nullptr, a.status, a.counters,
-                       PC != kPrimaryCacheNone ? static_cast<uint32_t*>(mk.prim_mem) : nullptr, qa);
+    const uint32_t* order = l.list ? l.list : (cost_order && mk.order_valid ? mk.order : nullptr);
+    typename dev::StageQueue<STAGE>::type qa; /* only a head has a queue argument */
+    if constexpr (STAGE == dev::kStageHead) qa = l.q;
+    hipLaunchKernelGGL((dev::pt_megakernel<COUNT, DIAG, SK, PAIRS, SINGLE, REUSE, PC, A, STAGE>),
+                       dim3(l.list ? l.grid : tiles), dim3(64), 0, l.stream, a.sd, a.materials, a.spheres, a.draws,
+                       a.tri_records, a.image, a.wire, a.wire_ch, a.W, a.H, RowMap{a.y0, a.row_shift, a.row_gap},
+                       a.wire_rows, a.rows, l.tilesX, tiles, scatter, order, cost_order ? mk.cost : nullptr, a.status,
+                       a.counters, PC != kPrimaryCacheNone ? static_cast<uint32_t*>(mk.prim_mem) : nullptr, qa);
     return hipGetLastError();
+}
+
+/* the tail behind its head on the same stream: one wave per 64 entries of the queue's capacity */
+template <bool PAIRS, bool SINGLE, int A>
+static hipError_t launch_tail(const MkLaunch& l)
+{
+    const LaunchArgs& a = l.a;
+    hipLaunchKernelGGL((dev::pt_mk_tail<PAIRS, SINGLE, A>), dim3((l.q.cap + 63u) / 64u), dim3(64), 0, l.stream, a.sd,
+                       a.materials, a.spheres, a.draws, a.tri_records, a.image, a.wire, a.wire_ch, a.W, a.wire_rows,
+                       a.status, l.q);
+    return hipGetLastError();
+}
+
+/* The dispatcher: a runtime MkVariant becomes the kernels' template arguments. Every field combination has a number
+ * (mk_variant_code), each number a launch function, and only the combinations mk_variant_built admits have a kernel
+ * behind theirs -- so mk_variant.h is the list of the instances this file compiles. */
+template <uint32_t CODE>
+static hipError_t launch_variant(const MkLaunch& l)
+{
+    constexpr MkVariant v = mk_variant_decode(CODE);
+    if constexpr (!mk_variant_built(v)) return hipErrorInvalidValue;
+    else if constexpr (v.stage == kMkStageTail) return launch_tail<v.pairs, v.single, v.arith>(l);
+    else return launch_mega<v.count, v.diag, v.stack, v.pairs, v.single, v.reuse, v.pcache, v.arith, v.stage>(l);
+}
+template <size_t... CODE>
+static hipError_t mk_dispatch(const MkVariant& v, const MkLaunch& l, std::index_sequence<CODE...>)
+{
+    static constexpr hipError_t (*table[])(const MkLaunch&) = {&launch_variant<(uint32_t)CODE>...};
+    return mk_variant_built(v) ? table[mk_variant_code(v)](l) : hipErrorInvalidValue;
+}
+static hipError_t mk_dispatch(const MkVariant& v, const MkLaunch& l)
+{
+    return mk_dispatch(v, l, std::make_index_sequence<kMkVariantCodes>{});
 }
 
 __global__ void fill_iota(uint32_t* __restrict__ v, uint32_t n)
@@ -696,16 +507,26 @@ void mk_release(MkState& mk)
  * geometry, after its 4th and 16th and then every kResortEvery renders (a radix sort of one key per tile, ~tens of
  * microseconds). */
 constexpr uint32_t kResortEvery = 64;
+
+/* Replace one of the launch state's device buffers (the tile costs, the primary cache, the split queues) by a larger
+ * one, behind everything that may still read the old one: both pipes joined into the stream -- so the next piped render
+ * forks again, behind whatever the caller queues on the stream to initialise the new buffer -- then, when there is an
+ * old buffer, the stream synchronised and the buffer freed; then the allocation. The tile-cost buffer used to grow
+ * without the join: it is a no-op when no frame is pending on the pipes, and the safe direction otherwise. The caller
+ * zeroes its capacity first, so a failure leaves a buffer that the next render grows again. */
+static hipError_t mk_grow(MkState& mk, hipStream_t stream, void*& mem, size_t bytes)
+{
+    hipError_t e = mk_join(mk, stream);
+    if (e == hipSuccess && mem) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    if (mem) (void)hipFree(mem);
+    mem = nullptr;
+    return hipMalloc(&mem, bytes);
+}
+
 static hipError_t cost_order_prepare(const LaunchArgs& a, MkState& mk, uint32_t tiles, hipStream_t stream)
 {
     if (tiles > mk.cap) {
-        if (mk.mem) {
-            hipError_t e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) return e;
-            (void)hipFree(mk.mem);
-            mk.mem = nullptr;
-            mk.cap = 0;
-        }
         size_t temp = 0;
         hipError_t e = hipcub::DeviceRadixSort::SortPairsDescending(nullptr, temp, (const uint32_t*)nullptr,
                                                                     (uint32_t*)nullptr, (const uint32_t*)nullptr,
@@ -713,10 +534,10 @@ static hipError_t cost_order_prepare(const LaunchArgs& a, MkState& mk, uint32_t 
         if (e != hipSuccess) return e;
         const size_t words = 5ull * tiles;
         const size_t bytes = ((words * 4ull + 255ull) & ~255ull) + temp;
-        void* m = nullptr;
-        e = hipMalloc(&m, bytes);
+        mk.cap = 0;
+        e = mk_grow(mk, stream, mk.mem, bytes);
         if (e != hipSuccess) return e;
-        mk.mem = m;
+        void* const m = mk.mem;
         uint32_t* u = static_cast<uint32_t*>(m);
         mk.cost = u;
         mk.keys = u + tiles;
@@ -761,69 +582,6 @@ static hipError_t cost_order_sort(MkState& mk, uint32_t tiles, hipStream_t strea
     e = hipGetLastError();
     mk.split_valid = e == hipSuccess;
     return e;
-}
-
-/* the render instantiations: sample reuse (samples > 1) x primary-cache mode of this render, in arithmetic mode A */
-template <int SK, bool PAIRS, bool SINGLE, int A>
-static hipError_t launch_mega_arith(const LaunchArgs& a, int pcmode, MkState& mk, hipStream_t stream, uint32_t tilesX,
-                                     uint32_t tiles, const uint32_t* list, uint32_t grid, const dev::SplitQueue* q)
-{
-    const bool reuse = a.sd.samples > 1u;
-    if constexpr (SK == 1) {
-        /* a split render (launch_megakernel: one sample, LDS stack): the head in this render's primary-cache mode, then
-         * the tail behind it on the same stream, one wave per 64 entries of the queue's capacity */
-        if (q != nullptr) {
-            constexpr int H = dev::kStageHead;
-            hipError_t e =
-                pcmode == kPrimaryCacheRead
-                    ? launch_mega<false, false, 1, PAIRS, SINGLE, false, kPrimaryCacheRead, A, H>(a, mk, stream, tilesX, tiles, list, grid, *q)
-                : pcmode == kPrimaryCacheWrite
-                    ? launch_mega<false, false, 1, PAIRS, SINGLE, false, kPrimaryCacheWrite, A, H>(a, mk, stream, tilesX, tiles, list, grid, *q)
-                    : launch_mega<false, false, 1, PAIRS, SINGLE, false, kPrimaryCacheNone, A, H>(a, mk, stream, tilesX, tiles, list, grid, *q);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((dev::pt_mk_tail<PAIRS, SINGLE, A>), dim3((q->cap + 63u) / 64u), dim3(64), 0, stream, a.sd,
-                               a.materials, a.spheres, a.draws, a.tri_records, a.image, a.wire, a.wire_ch, a.W, a.wire_rows,
-                               a.status, *q);
-            return hipGetLastError();
-        }
-    }
-    if (pcmode == kPrimaryCacheRead) /* its one-sample form holds the sample count as a constant: only for samples == 1 */
-        return a.sd.samples != 1u
-                   ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheRead, A>(a, mk, stream, tilesX, tiles, list, grid)
-                   : launch_mega<false, false, SK, PAIRS, SINGLE, false, kPrimaryCacheRead, A>(a, mk, stream, tilesX, tiles, list, grid);
-    if (pcmode == kPrimaryCacheWrite)
-        return reuse ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheWrite, A>(a, mk, stream, tilesX, tiles, list, grid)
-                     : launch_mega<false, false, SK, PAIRS, SINGLE, false, kPrimaryCacheWrite, A>(a, mk, stream, tilesX, tiles, list, grid);
-    return reuse ? launch_mega<false, false, SK, PAIRS, SINGLE, true, kPrimaryCacheNone, A>(a, mk, stream, tilesX, tiles, list, grid)
-                 : launch_mega<false, false, SK, PAIRS, SINGLE, false, kPrimaryCacheNone, A>(a, mk, stream, tilesX, tiles, list, grid);
-}
-
-/* WCPT_OPTION_ARITH (LaunchArgs::arith): the fast twin of every render instantiation; the count and diagnostics builds
- * have none (launch_mega_sk) */
-template <int SK, bool PAIRS, bool SINGLE>
-static hipError_t launch_mega_render(const LaunchArgs& a, int pcmode, MkState& mk, hipStream_t stream, uint32_t tilesX,
-                                     uint32_t tiles, const uint32_t* list, uint32_t grid, const dev::SplitQueue* q)
-{
-    return a.arith == WCPT_ARITH_FAST
-               ? launch_mega_arith<SK, PAIRS, SINGLE, WCPT_ARITH_FAST>(a, pcmode, mk, stream, tilesX, tiles, list, grid, q)
-               : launch_mega_arith<SK, PAIRS, SINGLE, WCPT_ARITH_EXACT>(a, pcmode, mk, stream, tilesX, tiles, list, grid, q);
-}
-
-/* pcmode: the render's primary-cache mode (the COUNT / DIAG builds never read or write the cache: their counters are
- * the reference's) */
-template <bool PAIRS, bool SINGLE>
-static hipError_t launch_mega_sk(const LaunchArgs& a, int mode, int stack_kind, int pcmode, MkState& mk, hipStream_t stream,
-                                 uint32_t tilesX, uint32_t tiles, const uint32_t* list = nullptr, uint32_t grid = 0,
-                                 const dev::SplitQueue* q = nullptr)
-{
-    if (stack_kind == 0) {
-        if (mode == kModeRender) return launch_mega_render<0, PAIRS, SINGLE>(a, pcmode, mk, stream, tilesX, tiles, list, grid, nullptr);
-        if (mode == kModeCount) return launch_mega<true, false, 0, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
-        return launch_mega<true, true, 0, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
-    }
-    if (mode == kModeRender) return launch_mega_render<1, PAIRS, SINGLE>(a, pcmode, mk, stream, tilesX, tiles, list, grid, q);
-    if (mode == kModeCount) return launch_mega<true, false, 1, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
-    return launch_mega<true, true, 1, PAIRS, SINGLE>(a, mk, stream, tilesX, tiles, list, grid);
 }
 
 hipError_t mk_join(MkState& mk, hipStream_t stream)
@@ -880,8 +638,6 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
         e = cost_order_prepare(a, mk, tiles, stream);
         if (e != hipSuccess) return e;
     }
-    /* one draw command (the reference's case): the single-draw instantiation, without the draw loop */
-    const bool single = a.sd.drawCommandCount == 1u;
     /* Primary cache (primary_cache_key.h has the rule). Counting runs leave it as it is. A write needs no join of its
      * own, and neither does the read that follows it: a pixel belongs to the same pipe while the tile order stands, and
      * every re-sort, new geometry or other kernel joins both pipes into the stream first (above and below), so the
@@ -897,17 +653,10 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
     }
     if (pcmode == kPrimaryCacheWrite) {
         mk.prim_valid = false;
-        const uint64_t bytes = (uint64_t)tiles * 64ull * (single ? 8ull : 12ull);
-        if (bytes > mk.prim_bytes) { /* grows like mk.mem: behind everything that may still read the old one */
-            if (mk.prim_mem) {
-                e = mk_join(mk, stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(stream);
-                if (e != hipSuccess) return e;
-                (void)hipFree(mk.prim_mem);
-                mk.prim_mem = nullptr;
-                mk.prim_bytes = 0;
-            }
-            e = hipMalloc(&mk.prim_mem, bytes);
+        const uint64_t bytes = (uint64_t)tiles * 64ull * (a.sd.drawCommandCount == 1u ? 8ull : 12ull) /* pt_device.h prim_cache_lane */;
+        if (bytes > mk.prim_bytes) {
+            mk.prim_bytes = 0;
+            e = mk_grow(mk, stream, mk.prim_mem, bytes);
             if (e != hipSuccess) return e;
             mk.prim_bytes = bytes;
         }
@@ -919,16 +668,15 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
     const uint32_t cut = mk_split_cut(a.mk_split, mode == kModeRender && stack_kind == 1, a.sd.samples,
                                       a.sd.maxBounceCount, tiles, 16ull * (uint64_t)mk.cus, a.triangles);
     const MkSplitLayout lay = mk_split_layout(tiles, pipes);
-    if (cut != 0u && lay.entries > mk.split_entries) { /* grows like mk.prim_mem; first: both counters of each pipe zero */
-        e = mk_join(mk, stream);
-        if (e == hipSuccess && mk.split_mem) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return e;
-        if (mk.split_mem) (void)hipFree(mk.split_mem);
-        mk.split_mem = nullptr;
+    /* the instance or instances of this render: mk_variant.h has the rule */
+    const MkSelection sel = mk_variant_select(mode, stack_kind, a.pair_records, a.sd.drawCommandCount, a.sd.samples, pcmode,
+                                              a.arith, cut != 0u);
+    const bool split = sel.n == 2u;
+    if (split && lay.entries > mk.split_entries) { /* first: both counters of each pipe zero */
         mk.split_entries = 0;
         const size_t state_bytes = (size_t)lay.entries * kMkSplitEntryBytes;
         const size_t ctr_bytes = 2u * kMkPipes * kMkSplitCounterWords * sizeof(uint32_t);
-        e = hipMalloc(&mk.split_mem, state_bytes + ctr_bytes);
+        e = mk_grow(mk, stream, mk.split_mem, state_bytes + ctr_bytes);
         if (e != hipSuccess) return e;
         mk.split_ctr = reinterpret_cast<uint32_t*>(static_cast<char*>(mk.split_mem) + state_bytes);
         mk.split_parity[0] = mk.split_parity[1] = 0u;
@@ -937,22 +685,17 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
         mk.split_entries = lay.entries;
     }
     auto launch = [&](const LaunchArgs& la, hipStream_t s, const uint32_t* list, uint32_t grid, uint32_t p) {
-        dev::SplitQueue q = {};
-        if (cut != 0u) { /* pipe p's queue and this frame's counter; the pipe's next frame takes the other */
-            q.state = static_cast<uint32_t*>(mk.split_mem) + (size_t)dev::kSplitWords * lay.first[p];
-            q.count = mk.split_ctr + (size_t)(2u * p + mk.split_parity[p]) * kMkSplitCounterWords;
-            q.count_next = mk.split_ctr + (size_t)(2u * p + (mk.split_parity[p] ^ 1u)) * kMkSplitCounterWords;
-            q.cap = lay.cap[p];
-            q.cut = cut;
+        MkLaunch l = {la, mk, s, tilesX, tiles, list, grid, dev::SplitQueue{}};
+        if (split) { /* pipe p's queue and this frame's counter; the pipe's next frame takes the other */
+            l.q.state = static_cast<uint32_t*>(mk.split_mem) + (size_t)dev::kSplitWords * lay.first[p];
+            l.q.count = mk.split_ctr + (size_t)(2u * p + mk.split_parity[p]) * kMkSplitCounterWords;
+            l.q.count_next = mk.split_ctr + (size_t)(2u * p + (mk.split_parity[p] ^ 1u)) * kMkSplitCounterWords;
+            l.q.cap = lay.cap[p];
+            l.q.cut = cut;
         }
-        const dev::SplitQueue* qp = cut != 0u ? &q : nullptr;
-        const hipError_t le =
-            la.pair_records
-                ? (single ? launch_mega_sk<true, true>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid, qp)
-                          : launch_mega_sk<true, false>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid, qp))
-                : (single ? launch_mega_sk<false, true>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid, qp)
-                          : launch_mega_sk<false, false>(la, mode, stack_kind, pcmode, mk, s, tilesX, tiles, list, grid, qp));
-        if (le == hipSuccess && cut != 0u) mk.split_parity[p] ^= 1u;
+        hipError_t le = hipSuccess; /* the whole kernel, or the head and then its tail */
+        for (uint32_t i = 0; i < sel.n && le == hipSuccess; i++) le = mk_dispatch(sel.v[i], l);
+        if (le == hipSuccess && split) mk.split_parity[p] ^= 1u;
         return le;
     };
     if (pipes) {
@@ -980,7 +723,7 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
     } else {
         e = launch(a, stream, nullptr, 0, 0u);
     }
-    if (e == hipSuccess && cut != 0u) mk.split_renders++;
+    if (e == hipSuccess && split) mk.split_renders++;
     if (e == hipSuccess && pcmode == kPrimaryCacheWrite) {
         mk.prim_key = *a.prim_key;
         mk.prim_valid = true;
@@ -998,51 +741,6 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
         return cost_order_sort(mk, tiles, stream);
     }
     return hipSuccess;
-}
-
-hipError_t launch_selftest(int fn, const uint32_t* in, const uint32_t* in2, uint32_t* out, uint32_t n, hipStream_t stream)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(dev::pt_selftest, dim3((n + 255u) / 256u), dim3(256), 0, stream, fn, in, in2, out, n);
-    return hipGetLastError();
-}
-
-bool selftest_geometry_words(int fn, uint32_t& in_words, uint32_t& out_words)
-{
-    static const uint32_t words[8][2] = {{15, 1}, {24, 4}, {24, 4}, {10, 1}, {11, 7}, {8, 7}, {3, 6}, {33, 10}};
-    if (fn < 0 || fn > 7) return false;
-    in_words = words[fn][0];
-    out_words = words[fn][1];
-    return true;
-}
-
-hipError_t launch_selftest_geometry(int fn, int arith, const uint32_t* in, uint32_t in_words, uint32_t* out,
-                                    uint32_t out_words, uint32_t n, hipStream_t stream)
-{
-    if (n == 0) return hipSuccess;
-    const dim3 grid((n + 255u) / 256u), block(256);
-#define WCPT_GEOMETRY_CASE(FN)                                                                                          \
-    case FN:                                                                                                            \
-        if (arith == WCPT_ARITH_FAST)                                                                                   \
-            hipLaunchKernelGGL((dev::pt_selftest_geometry<dev::kArithFast, FN>), grid, block, 0, stream, in, in_words, \
-                               out, out_words, n);                                                                      \
-        else                                                                                                            \
-            hipLaunchKernelGGL((dev::pt_selftest_geometry<dev::kArithExact, FN>), grid, block, 0, stream, in, in_words, \
-                               out, out_words, n);                                                                      \
-        break;
-    switch (fn) {
-        WCPT_GEOMETRY_CASE(0)
-        WCPT_GEOMETRY_CASE(1)
-        WCPT_GEOMETRY_CASE(2)
-        WCPT_GEOMETRY_CASE(3)
-        WCPT_GEOMETRY_CASE(4)
-        WCPT_GEOMETRY_CASE(5)
-        WCPT_GEOMETRY_CASE(6)
-        WCPT_GEOMETRY_CASE(7)
-    default: return hipErrorInvalidValue;
-    }
-#undef WCPT_GEOMETRY_CASE
-    return hipGetLastError();
 }
 
 } // namespace wcpt
