@@ -5,7 +5,8 @@
 Each variant is a comma list of option=value: stack=<0|1>, kernel=<0|2>, order=<0|1|2>, pipes=<1..4>, deindex=<0|1> (mesh re-laid out in
 BVH leaf order with identity indices: same triangles, same results, soup-like locality), arith=<0|1> (WCPT_OPTION_ARITH:
 1 = the megakernel's fast-arithmetic instances), mk_split=<-1|0|k> (WCPT_OPTION_MK_SPLIT: the megakernel cut before segment
-k into a head and a compacted tail launch; -1 = the automatic rule). Prints the median ms/frame (HIP events on the context stream) and
+k into a head and a compacted tail launch; -1 = the automatic rule), tiny=<-1|0|1> (WCPT_OPTION_MK_TINY_TREE: a root leaf
+or a root over two leaves walked without the traversal loop). Prints the median ms/frame (HIP events on the context stream) and
 Mray/s. With --check, variants of the same arith are compared bit for bit; variants of different arith by the
 statistics of the fast mode's stated tolerance (wcpt.h WCPT_OPTION_ARITH): diverged pixels (some channel off by more than
 1e-5 * max(1, |ref|), or a finiteness mismatch), the median relative difference, mean |d| and the bit-equal share.
@@ -89,6 +90,7 @@ def main():
             ctx.set_option(wcpt._lib.OPTION_WF_PIPES, int(o.get("pipes", wcpt._lib.DEFAULT_WF_PIPES)))
             ctx.set_option(wcpt._lib.OPTION_ARITH, int(o.get("arith", 0)))
             ctx.set_option(wcpt._lib.OPTION_MK_SPLIT, int(o.get("mk_split", -1)))
+            ctx.set_option(wcpt._lib.OPTION_MK_TINY_TREE, int(o.get("tiny", -1)))
             dev = scenes[o.get("deindex", "0")]
             ctx.profile_begin()
             for sd in sds:

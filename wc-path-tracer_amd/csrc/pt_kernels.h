@@ -7,6 +7,7 @@
 
 #include "../../include/wcpt.h"
 #include "mk_split_rule.h"
+#include "mk_tiny_rule.h"
 #include "mk_variant.h"
 #include "primary_cache_key.h"
 #include "row_map.h"
@@ -39,6 +40,7 @@ struct LaunchArgs {
     bool wf_fast;                /* wavefront trace: draw 0 has packed stack refs, 24-bit record offsets, leaves of < 255
                                     index positions on derived records (kTriFlagSmallLeaves, kTriFlagLeafRecords) and a known
                                     node count (table flags 1|2|4|8, word 2 high half > 0) */
+    bool tiny_tree = false;      /* draw 0's table flag kTriFlagTinyTree is set (mk_tiny_rule.h, WCPT_OPTION_MK_TINY_TREE) */
     int mk_split = kMkSplitAuto;  /* megakernel render launches: WCPT_OPTION_MK_SPLIT (mk_split_rule.h) */
     int arith = WCPT_ARITH_EXACT; /* megakernel render launches: WCPT_ARITH_FAST takes the fast instances (WCPT_OPTION_ARITH) */
     uint32_t mk_tile_order;      /* static megakernel: 0 XCD-banded, 1 scattered, 2 auto, 3-6 striped bands (WCPT_OPTION_MK_TILE_ORDER) */
@@ -180,6 +182,7 @@ struct MkState {
     uint32_t* split_ctr = nullptr;            /* [pipe][2][kMkSplitCounterWords] */
     uint32_t split_parity[2] = {0u, 0u};
     uint64_t split_renders = 0;               /* renders that ran as head + tail (wcpt_mk_split_stats) */
+    uint64_t tiny_renders = 0;                /* renders whose instances walked a tiny tree (wcpt_mk_tiny_tree_stats) */
 };
 constexpr uint32_t kMkPipes = 2;
 void mk_release(MkState& mk);
@@ -207,7 +210,8 @@ constexpr uint32_t kPrimPairRecordBytes = 112;
 hipError_t launch_build_primary_pairs(const void* pairs, uint32_t npairs, float ox, float oy, float oz, void* out,
                                       hipStream_t stream);
 /* *flags (zeroed here): bit 0 when some leaf of the BVH has triangleCount >= 255 (pt_device.h kRefFetch), bit 1 when
- * some leaf's triangles are not all derived records of the draw's `triangles` (pt_device.h kTriFlagLeafRecords) */
+ * some leaf's triangles are not all derived records of the draw's `triangles` (pt_device.h kTriFlagLeafRecords), bit 2
+ * when the tree is tiny (mk_tiny_rule.h) */
 hipError_t launch_scan_leaf_counts(const void* bvh, uint32_t nodes, uint32_t triangles, uint32_t* flags,
                                    hipStream_t stream);
 hipError_t launch_build_tri_records(const uint32_t* indices, const float* vertices, uint32_t triangles,

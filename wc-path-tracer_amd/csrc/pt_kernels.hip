@@ -18,6 +18,7 @@
 
 #include <utility>
 
+#include "mk_tiny_rule.h"
 #include "pt_device.h"
 #include "pt_kernels.h"
 
@@ -297,6 +298,13 @@ __global__ __launch_bounds__(256) void scan_leaf_counts(const wcpt_node* __restr
     if (f) atomicOr(flags, f);
 }
 
+/* The tiny-tree rule (mk_tiny_rule.h) on the BVH buffer's nodes: *flags |= 4 for a root leaf or a root over two leaves,
+ * each on the draw's derived records. One thread; behind scan_leaf_counts on the same stream. */
+__global__ void scan_tiny_tree(const wcpt_node* __restrict__ bvh, uint32_t nodes, uint32_t lim3, uint32_t* __restrict__ flags)
+{
+    if (blockIdx.x == 0u && threadIdx.x == 0u && mk_tiny_leaves(bvh, nodes, lim3) != 0u) atomicOr(flags, 4u);
+}
+
 __global__ __launch_bounds__(256) void build_tri_records(const uint32_t* __restrict__ idx, const float* __restrict__ vtx,
                                                          uint32_t ntri, uint32_t nvert, float4* __restrict__ singles,
                                                          float4* __restrict__ out)
@@ -371,6 +379,10 @@ hipError_t launch_scan_leaf_counts(const void* bvh, uint32_t nodes, uint32_t tri
     if (e != hipSuccess || nodes == 0) return e;
     hipLaunchKernelGGL(dev::scan_leaf_counts, dim3((nodes + 255u) / 256u), dim3(256), 0, stream,
                        static_cast<const wcpt_node*>(bvh), nodes, 3u * triangles, flags);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(dev::scan_tiny_tree, dim3(1), dim3(1), 0, stream, static_cast<const wcpt_node*>(bvh), nodes,
+                       3u * triangles, flags);
     return hipGetLastError();
 }
 
@@ -724,6 +736,10 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
         e = launch(a, stream, nullptr, 0, 0u);
     }
     if (e == hipSuccess && split) mk.split_renders++;
+    /* the instances that hold the tiny-tree walk (pt_device.h kTinyWalk), on a draw whose table flag is set */
+    if (e == hipSuccess && mode == kModeRender && a.tiny_tree && split && sel.v[0].pairs && sel.v[0].single &&
+        sel.v[0].arith == WCPT_ARITH_EXACT)
+        mk.tiny_renders++;
     if (e == hipSuccess && pcmode == kPrimaryCacheWrite) {
         mk.prim_key = *a.prim_key;
         mk.prim_valid = true;

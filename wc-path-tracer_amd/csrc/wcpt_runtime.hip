@@ -161,6 +161,7 @@ struct wcpt_context {
     int tri_cache = 1;                 /* WCPT_OPTION_TRIANGLE_CACHE */
     int prim_cache = 1;                /* WCPT_OPTION_PRIMARY_CACHE (active only with tri_cache) */
     int mk_split = wcpt::kMkSplitAuto; /* WCPT_OPTION_MK_SPLIT */
+    int mk_tiny_tree = wcpt::kMkTinyAuto; /* WCPT_OPTION_MK_TINY_TREE */
     int packed_refs = 1;               /* WCPT_OPTION_PACKED_REFS */
     int wf_fetch = -1;                 /* WCPT_OPTION_WF_FETCH */
     int wf_persist = -1;               /* WCPT_OPTION_WF_PERSIST */
@@ -190,7 +191,7 @@ struct wcpt_context {
         uint64_t gen = 0, draws = 0;
         uint32_t n = 0;
         uint32_t origin[3] = {0, 0, 0};
-        bool pair_records = false, wf_fast = false;
+        bool pair_records = false, wf_fast = false, tiny_tree = false;
         uint64_t triangles = 0; /* of all draws (LaunchArgs::triangles) */
         int kernel_run = WCPT_KERNEL_MEGAKERNEL;
     } prep;
@@ -375,6 +376,7 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
     const uint32_t n = sd.drawCommandCount;
     a.tri_records = nullptr;
     a.wf_fast = false;
+    a.tiny_tree = false;
     if (n == 0) {
         /* WCPT_KERNEL_AUTO with no draws: the megakernel (the rule below); an explicit choice stands */
         ctx->kernel_run = ctx->kernel != WCPT_KERNEL_AUTO ? ctx->kernel : WCPT_KERNEL_MEGAKERNEL;
@@ -387,6 +389,7 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
         std::memcmp(pc.origin, sd.position, sizeof(pc.origin)) == 0) {
         a.pair_records = pc.pair_records;
         a.wf_fast = pc.wf_fast;
+        a.tiny_tree = pc.tiny_tree;
         a.triangles = pc.triangles;
         ctx->kernel_run = pc.kernel_run;
         a.tri_records = ctx->d_tri_table;
@@ -415,6 +418,7 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
         std::memcpy(pc.origin, origin, sizeof(pc.origin));
         a.pair_records = pc.pair_records;
         a.wf_fast = pc.wf_fast;
+        a.tiny_tree = pc.tiny_tree;
         a.triangles = pc.triangles;
         ctx->kernel_run = pc.kernel_run;
         a.tri_records = ctx->d_tri_table;
@@ -527,6 +531,8 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
             }
             if (!(t.leaf_flags & 1u)) flags |= 4u; /* pt_device.h kTriFlagSmallLeaves */
             if (!(t.leaf_flags & 2u)) flags |= 8u; /* pt_device.h kTriFlagLeafRecords */
+            /* pt_device.h kTriFlagTinyTree: the scan's own rule (mk_tiny_rule.h), where the option allows the walk */
+            if (wcpt::mk_tiny_enabled(ctx->mk_tiny_tree, (t.leaf_flags & 4u) ? 1u : 0u)) flags |= 16u;
         }
         flags |= (uint64_t)nvert << 32;                 /* pt_device.h draw_vertex_count: bounds the index path */
         /* word 2: ntri, and in its high half the BVH node count when packed refs apply (the buffer-resource node loads
@@ -546,6 +552,7 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
     a.triangles = tris_all;
     /* the wavefront trace's one-draw fast layout: packed stack refs, 24-bit record offsets, buffer-resource node loads */
     a.wf_fast = n == 1 && (ctx->tri_table[3] & 15u) == 15u && (ctx->tri_table[2] >> 32) > 0;
+    a.tiny_tree = n == 1 && (ctx->tri_table[3] & 16u) != 0u;
     /* pair leaves address a draw's pair records with 32-bit byte offsets (pt_device.h load_pair_at) */
     a.pair_records = tris_max <= kPairMaxTriangles &&
                      (ctx->pair_records == 1 ||
@@ -628,6 +635,7 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
         std::memcpy(pc.origin, sd.position, sizeof(pc.origin));
         pc.pair_records = a.pair_records;
         pc.wf_fast = a.wf_fast;
+        pc.tiny_tree = a.tiny_tree;
         pc.triangles = a.triangles;
         pc.kernel_run = ctx->kernel_run;
     }
@@ -1108,6 +1116,12 @@ int wcpt_set_option(wcpt_context* ctx, int option, int value)
             return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "megakernel split %d", value);
         ctx->mk_split = value;
         return WCPT_SUCCESS;
+    case WCPT_OPTION_MK_TINY_TREE:
+        if (value < wcpt::kMkTinyAuto || value > 1)
+            return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "megakernel tiny tree %d", value);
+        if (ctx->mk_tiny_tree != value) ctx->generation++; /* the draw's table flag is part of the cached frame preparation */
+        ctx->mk_tiny_tree = value;
+        return WCPT_SUCCESS;
     case WCPT_OPTION_ARITH:
         if (value != WCPT_ARITH_EXACT && value != WCPT_ARITH_FAST)
             return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "arithmetic mode %d", value);
@@ -1456,6 +1470,13 @@ int wcpt_mk_split_stats(wcpt_context* ctx, uint64_t* renders)
 {
     if (!ctx) return set_error(nullptr, WCPT_ERROR_INVALID_HANDLE, "null context");
     if (renders) *renders = ctx->mk.split_renders;
+    return WCPT_SUCCESS;
+}
+
+int wcpt_mk_tiny_tree_stats(wcpt_context* ctx, uint64_t* renders)
+{
+    if (!ctx) return set_error(nullptr, WCPT_ERROR_INVALID_HANDLE, "null context");
+    if (renders) *renders = ctx->mk.tiny_renders;
     return WCPT_SUCCESS;
 }
 

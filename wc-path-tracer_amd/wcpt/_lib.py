@@ -60,6 +60,7 @@ OPTION_FRAME_OVERLAP = 15
 OPTION_PRIMARY_CACHE = 16
 OPTION_ARITH = 17       # the one option that changes results (wcpt.h WCPT_OPTION_ARITH)
 OPTION_MK_SPLIT = 18    # split renders: -1 automatic, 0 never, k = cut before segment k (csrc/mk_split_rule.h)
+OPTION_MK_TINY_TREE = 19  # tiny trees walked without the traversal loop: -1 automatic, 0 never, 1 on (csrc/mk_tiny_rule.h)
 ARITH_EXACT = 0
 ARITH_FAST = 1
 DEFAULT_WF_PIPES = 0  # wcpt_runtime.hip: by queue length (2 or 3)
@@ -181,6 +182,7 @@ _PROTOTYPES = {
     "wcpt_sync": (_i, [_p]),
     "wcpt_primary_cache_stats": (_i, [_p, C.POINTER(_u64), C.POINTER(_u64)]),
     "wcpt_mk_split_stats": (_i, [_p, C.POINTER(_u64)]),
+    "wcpt_mk_tiny_tree_stats": (_i, [_p, C.POINTER(_u64)]),
     "wcpt_render_counters": (_i, [_p, _p, _u64, _u64, _u64, C.POINTER(Counters)]),
     "wcpt_read_diagnostics": (_i, [_p, C.POINTER(C.c_uint64), _u32]),
     "wcpt_profile_begin": (_i, [_p]),

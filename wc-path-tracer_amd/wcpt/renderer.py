@@ -175,6 +175,12 @@ class Context:
         self._chk(lib.wcpt_mk_split_stats(self.h, C.byref(n)))
         return int(n.value)
 
+    def mk_tiny_tree_stats(self) -> int:
+        """The renders that walked a tiny tree without the traversal loop (WCPT_OPTION_MK_TINY_TREE)."""
+        n = C.c_uint64(0)
+        self._chk(lib.wcpt_mk_tiny_tree_stats(self.h, C.byref(n)))
+        return int(n.value)
+
     def render_counters(self, sd: np.ndarray, materials: int, spheres: int, draws: int,
                         diagnostics: bool = False) -> dict:
         """Reference-algorithm work counters of one frame (COUNTER_FIELDS); with diagnostics=True also the
