@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../include/wcpt.h"
+#include "../wc-path-tracer_amd/csrc/frame_prep.h"
 #include "../wc-path-tracer_amd/csrc/mk_variant.h"
 
 static int failures = 0;
@@ -206,6 +207,48 @@ int main(int argc, char** argv)
                                     CHECK(wcpt::mk_variant_code(s.v[i]) < wcpt::kMkVariantCodes);
                                 }
                             }
+
+    /* 6. frame preparation's rules (frame_prep.h, host only) at their boundaries: no overflow, no shift past a word */
+    for (uint32_t ntri : {0u, 1u, 2u, 5u, 6u, 1u << 26, 0xFFFFFFFFu / 3u}) {
+        const wcpt::RecordLayout l = wcpt::record_layout(ntri);
+        CHECK(l.pair_offset % 256u == 0u && l.pair_offset >= 48ull * ntri && l.bytes >= l.pair_offset + 40ull * ntri);
+        CHECK(l.prim_pairs == ((uint64_t)ntri + 1u) / 2u && l.prim_bytes == 112u * l.prim_pairs);
+    }
+    CHECK(wcpt::vertex_bound(true, ~0ull) == 0xFFFFFFFFu && wcpt::vertex_bound(true, 35) == 2u);
+    CHECK(wcpt::vertex_bound(false, 0) == 0xFFFFFFFFu);
+    CHECK(wcpt::bvh_node_count(false, ~0ull) == wcpt::kNodesUnknown && wcpt::bvh_node_count(true, ~0ull) == ~0ull / 32u);
+    CHECK(wcpt::leaf_estimate(true, ~0ull, 7) == (~0ull / 32u + 1u) / 2u && wcpt::leaf_estimate(false, ~0ull, 7) == 7u);
+    for (uint64_t nodes : {(uint64_t)0, (uint64_t)3, ((uint64_t)1 << 24) - 1u, (uint64_t)1 << 24, wcpt::kNodesUnknown})
+        for (uint32_t ic : {0u, 102u, (1u << 24) - 1u, 1u << 24, 0xFFFFFFFFu})
+            for (uint32_t scan = 0; scan < 8u; scan++)
+                for (int tiny = -1; tiny <= 1; tiny++)
+                    for (int k = 0; k < 4; k++) {
+                        const bool fits = nodes < (1ull << 24) && ic < (1u << 24);
+                        CHECK(wcpt::draw_needs_scan(k & 1, (k & 2) != 0, nodes, ic) == (k == 3 && fits));
+                        const wcpt::DrawWords w = wcpt::draw_words(k & 1, (k & 2) != 0, nodes, ic, scan, tiny, 0xFFFFFFFFu);
+                        CHECK((uint32_t)w.word2 == ic / 3u && (w.flags >> 32) == 0xFFFFFFFFu);
+                        CHECK(((w.flags & wcpt::kTriFlagPackedRefs) != 0u) == ((k & 1) && fits));
+                        CHECK((w.word2 >> 32) == ((k & 1) && fits ? nodes : 0u));
+                        if (k != 3 || !fits) CHECK((w.flags & 0xFFFFFFFCull) == 0u);
+                    }
+    CHECK(wcpt::check_draw_args(30, 1, 1, true, 120) == wcpt::kDrawArgsOk);
+    CHECK(wcpt::check_draw_args(33, 1, 1, true, 120) == wcpt::kDrawIndexCountPastBuffer);
+    CHECK(wcpt::check_draw_args(0xFFFFFFFFu, 1, 1, true, ~0ull) == wcpt::kDrawArgsOk);
+    CHECK(wcpt::check_draw_args(0xFFFFFFFFu, 1, 1, true, 0) == wcpt::kDrawIndexCountPastBuffer);
+    CHECK(wcpt::check_draw_args(2, 0, 0, false, 0) == wcpt::kDrawArgsOk);
+    CHECK(wcpt::check_draw_args(3, 0, 1, false, 0) == wcpt::kDrawNullBuffer);
+    for (uint32_t n : {0u, 1u, 2u, 0xFFFFFFFFu})
+        for (uint64_t tris : {0ull, 7ull, 8ull, 1ull << 26, (1ull << 26) + 1u, ~0ull})
+            for (uint64_t leaves : {0ull, 2ull, ~0ull})
+                for (int pair = -1; pair <= 1; pair++)
+                    for (int kernel = 0; kernel <= 2; kernel++) {
+                        const wcpt::FramePlan p = wcpt::frame_plan(n, ~0ull, ~0ull, tris, leaves, tris, pair, kernel);
+                        CHECK(p.kernel_run == WCPT_KERNEL_MEGAKERNEL || p.kernel_run == WCPT_KERNEL_WAVEFRONT);
+                        CHECK(kernel == WCPT_KERNEL_AUTO || p.kernel_run == kernel);
+                        CHECK(p.want_primary == (p.pair_records && p.kernel_run == WCPT_KERNEL_MEGAKERNEL));
+                        CHECK((p.wf_fast || p.tiny_tree) == (n == 1u));
+                        if (n == 0u || tris > wcpt::kPairMaxTriangles || pair == 0) CHECK(!p.pair_records);
+                    }
     std::printf("host sanitizer driver: %d failed checks\n", failures);
     return failures ? 1 : 0;
 }

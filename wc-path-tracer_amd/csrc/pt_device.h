@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/wcpt.h"
+#include "frame_prep.h"
 #include "mk_split_rule.h"
 #include "row_map.h"
 #include "wcpt_composite.h"
@@ -703,23 +704,12 @@ __device__ __forceinline__ float rayTriangle(const Ray& r, f3 a, f3 b, f3 c) { r
  * The reference's BVH keeps each leaf's index triples contiguous (PathTracingRenderer.jai:233), so a leaf's
  * records are contiguous. A leaf whose first index position is not a multiple of 3 (never produced by the
  * reference's builder) or that reaches past the draw's indexCount uses the index path.
- * Per-draw table entry: {single record address, pair record address, triangle count, flags | vertex count << 32,
- * primary-ray pair record address or 0} (5 x u64). */
-constexpr uint32_t kTriTableWords = 5;
-constexpr uint64_t kTriFlagPackedRefs = 1u; /* table word 3: stack entries may carry (left, count) */
-constexpr uint64_t kTriFlagIndex24 = 2u;    /* table word 3: the draw's indexCount is < 2^24 */
-constexpr uint64_t kTriFlagSmallLeaves = 4u; /* table word 3: every node's triangleCount is < kRefFetch, so every packed
-                                                stack entry carries its node's (left, count) */
-constexpr uint64_t kTriFlagLeafRecords = 8u; /* table word 3: every leaf starts at a triangle boundary and ends within the
-                                                draw's derived records, so each leaf triangle at index position p is
-                                                single record p / 3 (byte offset 16 p) */
-constexpr uint64_t kTriFlagTinyTree = 16u;  /* table word 3: the BVH is a root leaf or a root over two leaves, each on
-                                                derived records (mk_tiny_rule.h), and WCPT_OPTION_MK_TINY_TREE allows the
-                                                walk without the traversal loop (tiny_walk) */
+ * The per-draw table entry (kTriTableWords x u64, word indices kTriWord*, flags kTriFlag*) and the record sizes are
+ * declared once for the kernels and the runtime: frame_prep.h. */
 /* table word 3, bits 32..63: vertices in the draw's vertex buffer (0xFFFFFFFF: unknown, not a context buffer) */
 __device__ __forceinline__ uint32_t draw_vertex_count(const uint64_t* __restrict__ tri_records, uint32_t draw)
 {
-    return (uint32_t)(tri_records[kTriTableWords * draw + 3u] >> 32);
+    return (uint32_t)(tri_records[kTriTableWords * draw + kTriWordFlags] >> 32);
 }
 typedef const WCPT_GLOBAL v4f* gtri_ptr;
 struct TriE { f3 a, e1, e2; };
@@ -733,7 +723,7 @@ __device__ __forceinline__ TriE load_tri(gtri_ptr t, uint32_t k)
     e.e2 = mk3(r1.z, r1.w, r2.x);
     return e;
 }
-constexpr uint32_t kPairRecordFloat4s = 5;
+constexpr uint32_t kPairRecordFloat4s = kPairRecordBytes / 16u; /* 5 */
 struct TriPair { v2f ax, ay, az, e1x, e1y, e1z, e2x, e2y, e2z; };
 __device__ __forceinline__ TriPair load_pair(gtri_ptr t, uint32_t j)
 {
@@ -747,8 +737,7 @@ __device__ __forceinline__ TriPair load_pair(gtri_ptr t, uint32_t j)
     p.e2z = r4.xy;
     return p;
 }
-/* The pair record at byte offset `off` from the record base (pair j at off = 80 j). */
-constexpr uint32_t kPairRecordBytes = 16u * kPairRecordFloat4s;
+/* The pair record at byte offset `off` from the record base (pair j at off = kPairRecordBytes j). */
 constexpr uint32_t kNoTag = 0xFFFFFFFFu;
 
 __device__ __forceinline__ TriPair load_pair_at(const WCPT_GLOBAL char* base, uint32_t off)
@@ -824,8 +813,7 @@ __device__ __forceinline__ PairHit rayTrianglePair(const Ray& r, const TriPair& 
  * order, so the values are bit-identical) and the first segment of each sample tests its leaves from these records:
  * 51 instead of 68 VALU per pair. 112 B per pair: (e1x, e1y) (e1z, e2x) (e2y, e2z) (oax, oay) (oaz, qx) (qy, qz)
  * (tq, pad), each a float2 {triangle 2j, 2j+1}. */
-constexpr uint32_t kPrimPairFloat4s = 7;
-constexpr uint32_t kPrimPairRecordBytes = 16u * kPrimPairFloat4s;
+constexpr uint32_t kPrimPairFloat4s = kPrimPairRecordBytes / 16u; /* 7 */
 struct TriPairP { v2f e1x, e1y, e1z, e2x, e2y, e2z, oax, oay, oaz, qx, qy, qz, tq; };
 template <class P>
 __device__ __forceinline__ TriPairP unpack_pairP(P q)
@@ -1260,8 +1248,8 @@ __device__ __forceinline__ f3 triangle_normal(uint32_t prim, uint32_t draw, cons
                                               const uint64_t* __restrict__ tri_records)
 {
     const uint32_t k = prim / 3u;
-    if (tri_records && k * 3u == prim && k < (uint32_t)tri_records[kTriTableWords * draw + 2u]) {
-        const gtri_ptr t = (gtri_ptr)(uintptr_t)tri_records[kTriTableWords * draw];
+    if (tri_records && k * 3u == prim && k < (uint32_t)tri_records[kTriTableWords * draw + kTriWordCount]) {
+        const gtri_ptr t = (gtri_ptr)(uintptr_t)tri_records[kTriTableWords * draw + kTriWordSingles];
         const v4f r2 = t[3ull * k + 2u];
         return mk3(r2.y, r2.z, r2.w);
     }
@@ -1320,11 +1308,11 @@ __device__ __forceinline__ DrawGeom draw_geom(const wcpt_draw_command* __restric
     g.bvh = as_nodes(draws[i].bvhBuffer);
     g.indices = as_u32(draws[i].indexBuffer);
     g.vertices = as_f32(draws[i].vertexBuffer);
-    g.tris = (gtri_ptr)(uintptr_t)tri_records[kTriTableWords * i + (PAIRS ? 1u : 0u)];
-    g.ptris = PAIRS ? (gtri_ptr)(uintptr_t)tri_records[kTriTableWords * i + 4u] : nullptr;
-    g.ntri = (uint32_t)tri_records[kTriTableWords * i + 2u];
+    g.tris = (gtri_ptr)(uintptr_t)tri_records[kTriTableWords * i + (PAIRS ? kTriWordPairs : kTriWordSingles)];
+    g.ptris = PAIRS ? (gtri_ptr)(uintptr_t)tri_records[kTriTableWords * i + kTriWordPrimary] : nullptr;
+    g.ntri = (uint32_t)tri_records[kTriTableWords * i + kTriWordCount];
     g.nvert = draw_vertex_count(tri_records, i);
-    g.packed = (tri_records[kTriTableWords * i + 3u] & kTriFlagPackedRefs) != 0u;
+    g.packed = (tri_records[kTriTableWords * i + kTriWordFlags] & kTriFlagPackedRefs) != 0u;
     return g;
 }
 
@@ -1790,7 +1778,7 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
              * counters) is walked instead of this loop: one wave-uniform branch around the whole traversal */
             bool tiny = false;
             if constexpr (kTinyWalk<COUNT, DIAG, PAIRS, A, SPLIT>)
-                tiny = sd.drawCommandCount != 0u && (tri_records[3] & kTriFlagTinyTree) != 0u;
+                tiny = sd.drawCommandCount != 0u && (tri_records[kTriWordFlags] & kTriFlagTinyTree) != 0u;
             if (tiny) {
                 if constexpr (kTinyWalk<COUNT, DIAG, PAIRS, A, SPLIT>) tiny_walk<A>(ray, g, primary, rt, prim, cnt);
             } else if (sd.drawCommandCount != 0u && root_step<COUNT>(ray, g, rt, curLeft, curCount, cnt, rf)) {

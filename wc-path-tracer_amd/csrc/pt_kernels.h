@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/wcpt.h"
+#include "frame_prep.h"
 #include "mk_split_rule.h"
 #include "mk_tiny_rule.h"
 #include "mk_variant.h"
@@ -30,7 +31,7 @@ struct LaunchArgs {
     const wcpt_material* materials;
     const wcpt_sphere* spheres;
     const wcpt_draw_command* draws;
-    const uint64_t* tri_records; /* device table [drawCommandCount] of {singles, pairs, triangle count, -} */
+    const uint64_t* tri_records; /* device table [drawCommandCount] of kTriTableWords words (frame_prep.h) */
     uint64_t triangles = 0;      /* of all draw commands (the split rule's input, mk_split_rule.h) */
     bool pair_records;           /* megakernel: leaf tests on pair records (fat leaves) instead of singles */
     uint32_t wf_refill;          /* wavefront trace: idle lanes that trigger a ray fetch (1..64) */
@@ -39,7 +40,7 @@ struct LaunchArgs {
     int wf_persist;              /* path-persistent trace: -1 auto, 0 off, 1 wherever eligible (WCPT_OPTION_WF_PERSIST) */
     bool wf_fast;                /* wavefront trace: draw 0 has packed stack refs, 24-bit record offsets, leaves of < 255
                                     index positions on derived records (kTriFlagSmallLeaves, kTriFlagLeafRecords) and a known
-                                    node count (table flags 1|2|4|8, word 2 high half > 0) */
+                                    node count (kTriFlagsFastLayout, word 2 high half > 0) */
     bool tiny_tree = false;      /* draw 0's table flag kTriFlagTinyTree is set (mk_tiny_rule.h, WCPT_OPTION_MK_TINY_TREE) */
     int mk_split = kMkSplitAuto;  /* megakernel render launches: WCPT_OPTION_MK_SPLIT (mk_split_rule.h) */
     int arith = WCPT_ARITH_EXACT; /* megakernel render launches: WCPT_ARITH_FAST takes the fast instances (WCPT_OPTION_ARITH) */
@@ -199,19 +200,13 @@ hipError_t mk_join(MkState& mk, hipStream_t stream);
 
 /* Launch modes (kModeRender / kModeCount / kModeDiag): mk_variant.h */
 
-/* Derived triangle records (pt_device.h): triangle k = index positions 3k..3k+2 stored as (a, b - a, c - a);
- * singles: 48 B per triangle; pairs: 80 B per triangle pair (2j, 2j+1). */
-constexpr uint32_t kSingleRecordBytes = 48, kPairRecordBytes = 80;
-/* primary-ray pair records (pt_device.h TriPairP), built with launch_build_primary_pairs */
-constexpr uint32_t kPrimPairRecordBytes = 112;
-/* vertex_count bounds the vertex indices read (0xFFFFFFFF: unknown); a triangle with an index past it gets a NaN
- * record, which no ray accepts. */
+/* Derived triangle records (pt_device.h; their sizes and the table that points at them: frame_prep.h). vertex_count
+ * bounds the vertex indices read (0xFFFFFFFF: unknown); a triangle with an index past it gets a NaN record, which no
+ * ray accepts. */
 /* Primary-ray pair records (pt_device.h TriPairP) of `npairs` pair records for the camera origin (ox, oy, oz). */
 hipError_t launch_build_primary_pairs(const void* pairs, uint32_t npairs, float ox, float oy, float oz, void* out,
                                       hipStream_t stream);
-/* *flags (zeroed here): bit 0 when some leaf of the BVH has triangleCount >= 255 (pt_device.h kRefFetch), bit 1 when
- * some leaf's triangles are not all derived records of the draw's `triangles` (pt_device.h kTriFlagLeafRecords), bit 2
- * when the tree is tiny (mk_tiny_rule.h) */
+/* *flags (zeroed here): the BVH's kLeafScan* bits (frame_prep.h) against the draw's `triangles` derived records */
 hipError_t launch_scan_leaf_counts(const void* bvh, uint32_t nodes, uint32_t triangles, uint32_t* flags,
                                    hipStream_t stream);
 hipError_t launch_build_tri_records(const uint32_t* indices, const float* vertices, uint32_t triangles,

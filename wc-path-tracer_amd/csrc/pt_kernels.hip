@@ -282,10 +282,10 @@ __device__ __forceinline__ void tri_fields(const uint32_t* __restrict__ idx, con
     f[6] = e2.x; f[7] = e2.y; f[8] = e2.z;
 }
 
-/* The BVH's leaves against the fast layout's assumptions: *flags |= 1 when some leaf has triangleCount >= kRefFetch (a
- * stack entry of it would not carry its count), |= 2 when some leaf does not start at a triangle boundary or reaches
- * past the draw's derived records (first % 3 != 0 or first + count > lim3 = 3 * triangles: its triangles would need
- * the index path). */
+/* The BVH's leaves against the fast layout's assumptions (bits: frame_prep.h): *flags |= kLeafScanBigLeaf when some leaf
+ * has triangleCount >= kRefFetch (a stack entry of it would not carry its count), |= kLeafScanOffRecords when some leaf
+ * does not start at a triangle boundary or reaches past the draw's derived records (first % 3 != 0 or first + count >
+ * lim3 = 3 * triangles: its triangles would need the index path). */
 __global__ __launch_bounds__(256) void scan_leaf_counts(const wcpt_node* __restrict__ bvh, uint32_t nodes, uint32_t lim3,
                                                         uint32_t* __restrict__ flags)
 {
@@ -293,16 +293,16 @@ __global__ __launch_bounds__(256) void scan_leaf_counts(const wcpt_node* __restr
     if (i >= nodes) return;
     const uint32_t first = bvh[i].leftNodeOrTriangleIndex, count = bvh[i].triangleCount;
     if (count == 0u) return;
-    uint32_t f = count >= kRefFetch ? 1u : 0u;
-    if (first % 3u != 0u || first > lim3 || count > lim3 - first) f |= 2u;
+    uint32_t f = count >= kRefFetch ? kLeafScanBigLeaf : 0u;
+    if (first % 3u != 0u || first > lim3 || count > lim3 - first) f |= kLeafScanOffRecords;
     if (f) atomicOr(flags, f);
 }
 
-/* The tiny-tree rule (mk_tiny_rule.h) on the BVH buffer's nodes: *flags |= 4 for a root leaf or a root over two leaves,
- * each on the draw's derived records. One thread; behind scan_leaf_counts on the same stream. */
+/* The tiny-tree rule (mk_tiny_rule.h) on the BVH buffer's nodes: *flags |= kLeafScanTinyTree for a root leaf or a root
+ * over two leaves, each on the draw's derived records. One thread; behind scan_leaf_counts on the same stream. */
 __global__ void scan_tiny_tree(const wcpt_node* __restrict__ bvh, uint32_t nodes, uint32_t lim3, uint32_t* __restrict__ flags)
 {
-    if (blockIdx.x == 0u && threadIdx.x == 0u && mk_tiny_leaves(bvh, nodes, lim3) != 0u) atomicOr(flags, 4u);
+    if (blockIdx.x == 0u && threadIdx.x == 0u && mk_tiny_leaves(bvh, nodes, lim3) != 0u) atomicOr(flags, kLeafScanTinyTree);
 }
 
 __global__ __launch_bounds__(256) void build_tri_records(const uint32_t* __restrict__ idx, const float* __restrict__ vtx,
@@ -386,8 +386,6 @@ hipError_t launch_scan_leaf_counts(const void* bvh, uint32_t nodes, uint32_t tri
     return hipGetLastError();
 }
 
-static_assert(dev::kPrimPairRecordBytes == kPrimPairRecordBytes, "primary-ray pair record size");
-static_assert(dev::kPairRecordBytes == kPairRecordBytes, "pair record size");
 hipError_t launch_build_primary_pairs(const void* pairs, uint32_t npairs, float ox, float oy, float oz, void* out,
                                       hipStream_t stream)
 {

@@ -203,15 +203,15 @@ __device__ __forceinline__ Geom load_geom(const wcpt_draw_command* __restrict__ 
                                           const uint64_t* __restrict__ tri_records, uint32_t d)
 {
     Geom g;
-    g.tris = (gtri_ptr)(uintptr_t)tri_records[kTriTableWords * d];      /* single records */
-    g.ntri = (uint32_t)tri_records[kTriTableWords * d + 2u];
-    g.packed = (tri_records[kTriTableWords * d + 3u] & kTriFlagPackedRefs) != 0u;
-    g.idx24 = (tri_records[kTriTableWords * d + 3u] & kTriFlagIndex24) != 0u;
+    g.tris = (gtri_ptr)(uintptr_t)tri_records[kTriTableWords * d + kTriWordSingles];      /* single records */
+    g.ntri = (uint32_t)tri_records[kTriTableWords * d + kTriWordCount];
+    g.packed = (tri_records[kTriTableWords * d + kTriWordFlags] & kTriFlagPackedRefs) != 0u;
+    g.idx24 = (tri_records[kTriTableWords * d + kTriWordFlags] & kTriFlagIndex24) != 0u;
     g.lim3 = 3u * g.ntri;
     g.bvh = as_nodes(draws[d].bvhBuffer);
     g.indices = as_u32(draws[d].indexBuffer);
     g.vertices = as_f32(draws[d].vertexBuffer);
-    g.nodes = g.packed ? (uint32_t)(tri_records[kTriTableWords * d + 2u] >> 32) : 0u;
+    g.nodes = g.packed ? (uint32_t)(tri_records[kTriTableWords * d + kTriWordCount] >> 32) : 0u;
     g.rsrc = node_rsrc(g.bvh, g.nodes);
     g.trsrc = tri_rsrc(g.tris, g.idx24 ? g.ntri : 0u);
     return g;

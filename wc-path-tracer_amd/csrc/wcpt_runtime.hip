@@ -80,34 +80,24 @@ struct TriRecords {
     uint64_t pair_offset = 0;
     uint64_t build_id = 0;  /* incremented on every rebuild of the records */
     /* whether every node of the draw's BVH (address bvh, `bvh_nodes` nodes, buffer generation gen_bvh) has
-     * triangleCount < 255 (pt_device.h kTriFlagSmallLeaves) */
+     * triangleCount < 255 (frame_prep.h kTriFlagSmallLeaves) */
     uint64_t bvh = 0, gen_bvh = kUnknownGeneration;
     uint64_t bvh_nodes = 0;
     uint32_t bvh_ntri = 0;
-    uint32_t leaf_flags = 0;   /* launch_scan_leaf_counts */
+    uint32_t leaf_flags = 0;   /* launch_scan_leaf_counts: frame_prep.h kLeafScan* */
     bool leaves_valid = false;
-    /* primary-ray pair records (pt_device.h TriPairP) for the camera position `porigin` (bit patterns), derived from
-     * the pair records of build `pbuild` */
-    void* pmem = nullptr;   /* two copies of pcap bytes: the context stream's, then the overlap's pipe 1's (pmem1) */
+    /* primary-ray pair records (pt_device.h TriPairP): two copies of pcap bytes in pmem, the context stream's (state
+     * `prim`), then the overlap's pipe 1's (pmem1, state `prim1`). Pipe 1's copy is rebuilt on pipe 1's stream only, so
+     * neither copy is ever written while the other stream's frames read it (prep_pipe1). */
+    void* pmem = nullptr;
     uint64_t pcap = 0;
-    bool pvalid = false;
-    uint32_t porigin[3] = {0, 0, 0};
-    uint64_t pbuild = 0;
-    /* pipe 1's copy (frame overlap): rebuilt on pipe 1's stream only, so neither copy is ever written while the other
-     * stream's frames read it (prep_pipe1) */
-    bool pvalid1 = false;
-    uint32_t porigin1[3] = {0, 0, 0};
-    uint64_t pbuild1 = 0;
+    struct PrimCopy {
+        bool valid = false;
+        uint32_t origin[3] = {0, 0, 0}; /* the camera position the copy is derived for (bit patterns) */
+        uint64_t build = 0;             /* ... from the pair records of this build_id */
+    } prim, prim1;
     void* pmem1() const { return pmem ? static_cast<char*>(pmem) + pcap : nullptr; }
 };
-
-/* Pair records (packed two-triangle tests) pay off when leaves are fat: mean triangles per leaf >= this,
- * estimated as triangles / leaves with leaves = (nodes + 1) / 2 from the BVH buffer's size. Measured: the
- * Cornell box (17 per leaf) gains, the atrium (~2 per leaf) loses. */
-constexpr double kPairMinTrianglesPerLeaf = 4.0;
-/* Largest triangle count of a draw whose pair records are used: 40 B per triangle must stay addressable with 32-bit
- * byte offsets (2^26 triangles = 2.5 GiB of pair records); larger draws use single records. */
-constexpr uint64_t kPairMaxTriangles = 1ull << 26;
 
 /* Bytes per pixel of a gather payload format (wcpt.h WCPT_PAYLOAD_*) */
 uint64_t payload_pixel_bytes(uint32_t format) { return format == WCPT_PAYLOAD_DISPLAY_RGBA8 ? 4u : 4ull * format; }
@@ -191,9 +181,7 @@ struct wcpt_context {
         uint64_t gen = 0, draws = 0;
         uint32_t n = 0;
         uint32_t origin[3] = {0, 0, 0};
-        bool pair_records = false, wf_fast = false, tiny_tree = false;
-        uint64_t triangles = 0; /* of all draws (LaunchArgs::triangles) */
-        int kernel_run = WCPT_KERNEL_MEGAKERNEL;
+        wcpt::FramePlan plan;
     } prep;
     struct ValidCache {
         bool valid = false;
@@ -206,11 +194,10 @@ struct wcpt_context {
     uint64_t handoff_draws = 0;
     bool handoff_valid = false;
     std::vector<TriRecords> tri;       /* per draw command index */
-    std::vector<uint64_t> tri_table;   /* host image of d_tri_table: {address, ntri} per draw */
+    std::vector<uint64_t> tri_table;   /* host image of d_tri_table: kTriTableWords per draw (frame_prep.h) */
     uint64_t* d_tri_table = nullptr;   /* two tables of tri_table_cap draws: the context stream's, then pipe 1's, whose
-                                        * word 4 points at the pipe-1 copy of the primary-ray records */
+                                        * kTriWordPrimary points at the pipe-1 copy of the primary-ray records */
     uint32_t tri_table_cap = 0;        /* draws d_tri_table can hold */
-    bool prim_records = false;         /* the last preparation derived primary-ray records (table word 4) */
     std::string last_error;
     bool profiling = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -333,6 +320,26 @@ Buffer* buffer_at(wcpt_context* ctx, uint64_t addr, uint64_t& offset)
     return nullptr;
 }
 
+/* ---- frame preparation: what it decides is stated in frame_prep.h; what it does to the device is below ---------------- */
+
+/* One copy of a draw's primary-ray records (`copy` of the bytes at `dst`) brought to the camera position `origin` (bit
+ * patterns) and the records build `build`, on the stream that owns the copy; nothing is queued when it is there. */
+hipError_t bring_primary_copy(const TriRecords& t, TriRecords::PrimCopy& copy, void* dst, const uint32_t origin[3],
+                              uint64_t build, hipStream_t stream)
+{
+    if (copy.valid && copy.build == build && std::memcmp(copy.origin, origin, sizeof(copy.origin)) == 0) return hipSuccess;
+    float o[3];
+    std::memcpy(o, origin, sizeof(o));
+    const hipError_t e = wcpt::launch_build_primary_pairs(static_cast<const char*>(t.mem) + t.pair_offset,
+                                                          (uint32_t)wcpt::record_layout(t.ntri).prim_pairs, o[0], o[1], o[2],
+                                                          dst, stream);
+    if (e != hipSuccess) return e;
+    copy.valid = true;
+    copy.build = build;
+    std::memcpy(copy.origin, origin, sizeof(copy.origin));
+    return hipSuccess;
+}
+
 /* Frame overlap, pipe 1 (pt_kernels.hip launch_megakernel): before its launch, on its own stream, the pipe-1 copy of
  * each draw's primary-ray records is derived again when it is not of the frame's camera position and records build.
  * Only pipe 1's stream ever writes that copy and the context's stream the other, so a moving camera needs no join. */
@@ -340,89 +347,238 @@ hipError_t prep_pipe1(void* user, hipStream_t stream)
 {
     wcpt_context* ctx = static_cast<wcpt_context*>(user);
     for (TriRecords& t : ctx->tri) {
-        if (!t.pvalid || t.ntri == 0) continue;
-        if (t.pvalid1 && t.pbuild1 == t.pbuild && std::memcmp(t.porigin1, t.porigin, sizeof(t.porigin)) == 0) continue;
-        float o[3];
-        std::memcpy(o, t.porigin, sizeof(o));
-        const uint64_t npairs = ((uint64_t)t.ntri + 1u) / 2u;
-        const hipError_t e = wcpt::launch_build_primary_pairs(static_cast<const char*>(t.mem) + t.pair_offset,
-                                                              (uint32_t)npairs, o[0], o[1], o[2], t.pmem1(), stream);
+        if (!t.prim.valid || t.ntri == 0) continue;
+        const hipError_t e = bring_primary_copy(t, t.prim1, t.pmem1(), t.prim.origin, t.prim.build, stream);
         if (e != hipSuccess) return e;
-        t.pvalid1 = true;
-        t.pbuild1 = t.pbuild;
-        std::memcpy(t.porigin1, t.porigin, sizeof(t.porigin));
     }
     return hipSuccess;
 }
 
-void set_pipe1_records(wcpt_context* ctx, uint32_t n, wcpt::LaunchArgs& a)
+/* A frame's plan into its launch arguments and the context: the one exit of prepare_tri_records. With primary-ray
+ * records pipe 1 reads a table of its own and derives its copy before its launch; else both pipes read the one table. */
+void apply_plan(wcpt_context* ctx, const wcpt::FramePlan& p, uint32_t n, wcpt::LaunchArgs& a)
 {
-    a.tri_records_pipe1 = nullptr;
-    a.pipe1_prepare = nullptr;
-    a.pipe1_user = nullptr;
-    if (!ctx->prim_records || n == 0) return; /* no primary-ray records: both pipes read the one table */
-    a.tri_records_pipe1 = ctx->d_tri_table + 5ull * ctx->tri_table_cap;
-    a.pipe1_prepare = prep_pipe1;
-    a.pipe1_user = ctx;
+    a.pair_records = p.pair_records;
+    a.wf_fast = p.wf_fast;
+    a.tiny_tree = p.tiny_tree;
+    a.triangles = p.triangles;
+    ctx->kernel_run = p.kernel_run;
+    const bool pipe1 = p.want_primary && n != 0;
+    a.tri_records = n ? ctx->d_tri_table : nullptr;
+    a.tri_records_pipe1 = pipe1 ? ctx->d_tri_table + (uint64_t)wcpt::kTriTableWords * ctx->tri_table_cap : nullptr;
+    a.pipe1_prepare = pipe1 ? prep_pipe1 : nullptr;
+    a.pipe1_user = pipe1 ? ctx : nullptr;
 }
 
-/* Derive (or reuse) the triangle records of every draw command and point a.tri_records at the table. The draw
- * commands are read from the host copy of their buffer when every byte of them was written through
- * wcpt_buffer_upload and the triangle cache is on; otherwise from the device (a synchronous copy of 32 B per draw),
- * so that draw commands written by other means (hipMemcpy, the application's own kernels) are honoured with
- * WCPT_OPTION_TRIANGLE_CACHE = 0. */
+/* A device allocation that work queued on the context's stream may still read, replaced by one of `bytes`: that work
+ * is waited for only when there is an old allocation. */
+template <class T, class C>
+int grow(wcpt_context* ctx, T*& mem, C& cap, C new_cap, uint64_t bytes, const char* what)
+{
+    if (mem) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+        (void)hipFree(mem);
+    }
+    mem = nullptr;
+    cap = 0;
+    HIP_TRY(ctx, hipMalloc(&mem, bytes), what);
+    cap = new_cap;
+    return WCPT_SUCCESS;
+}
+
+/* The frame's n draw commands into dc: from the host copy of their buffer when every byte of them was written through
+ * wcpt_buffer_upload and the triangle cache is on (from_host); otherwise from the device, behind the pending frames (a
+ * synchronous copy of 32 B per draw), so that draw commands written by other means (hipMemcpy, the application's own
+ * kernels) are honoured with WCPT_OPTION_TRIANGLE_CACHE = 0. */
+int read_draw_commands(wcpt_context* ctx, uint64_t draws, uint32_t n, std::vector<wcpt_draw_command>& dc, bool& from_host)
+{
+    const uint64_t dbytes = (uint64_t)n * sizeof(wcpt_draw_command);
+    uint64_t off = 0;
+    Buffer* db = buffer_at(ctx, draws, off);
+    from_host = ctx->tri_cache && db && shadow_known(*db, off, dbytes);
+    dc.resize(n);
+    if (from_host) {
+        std::memcpy(dc.data(), db->shadow.data() + off, dbytes);
+        return WCPT_SUCCESS;
+    }
+    const int rc = join_pending(ctx);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(dc.data(), reinterpret_cast<const void*>(draws), dbytes, hipMemcpyDeviceToHost, ctx->stream),
+            "hipMemcpyAsync(draw commands)");
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(draw commands)");
+    return WCPT_SUCCESS;
+}
+
+/* The argument checks of draw command d (frame_prep.h check_draw_args; bi: its index buffer at offset oi, or null when
+ * the context does not know it), for the render and for render_validate alike. */
+int check_draw(wcpt_context* ctx, uint32_t d, const wcpt_draw_command& c, const Buffer* bi, uint64_t oi)
+{
+    const uint64_t left = bi ? bi->bytes - oi : 0;
+    switch (wcpt::check_draw_args(c.indexCount, c.vertexBuffer, c.indexBuffer, bi != nullptr, left)) {
+    case wcpt::kDrawIndexCountPastBuffer:
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT,
+                         "draw command %u: indexCount %u exceeds its index buffer (%llu bytes from offset %llu)", d,
+                         c.indexCount, (unsigned long long)left, (unsigned long long)oi);
+    case wcpt::kDrawNullBuffer:
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "draw command %u: null vertex/index buffer", d);
+    default: return WCPT_SUCCESS;
+    }
+}
+
+/* Word `word` of draw d in the host image of the table; true when that changed it. */
+bool set_table_word(wcpt_context* ctx, uint32_t d, uint32_t word, uint64_t value)
+{
+    uint64_t& w = ctx->tri_table[(uint64_t)wcpt::kTriTableWords * d + word];
+    if (w == value) return false;
+    w = value;
+    return true;
+}
+
+/* what the per-draw steps add up for frame_plan */
+struct PrepSums { uint64_t tris_all = 0, leaves_all = 0, tris_max = 0; };
+
+/* Draw d of a preparation miss: its argument checks, its triangle records (rebuilt unless the triangle cache holds
+ * them), the leaf scan of its BVH (once per BVH buffer generation; the one step that blocks the host) and its table
+ * words but the primary-ray records'. */
+int prepare_draw(wcpt_context* ctx, uint32_t d, const wcpt_draw_command& c, PrepSums& sums, bool& table_dirty)
+{
+    TriRecords& t = ctx->tri[d];
+    const uint64_t vb = c.vertexBuffer, ib = c.indexBuffer;
+    uint64_t ov = 0, oi = 0, ob = 0;
+    const Buffer* bv = buffer_at(ctx, vb, ov);
+    const Buffer* bi = buffer_at(ctx, ib, oi);
+    const Buffer* bb = buffer_at(ctx, c.bvhBuffer, ob);
+    const int rc = check_draw(ctx, d, c, bi, oi);
+    if (rc) return rc;
+    const uint64_t gv = bv ? bv->generation : kUnknownGeneration;
+    const uint64_t gi = bi ? bi->generation : kUnknownGeneration;
+    const uint32_t ntri = c.indexCount / 3u;
+    const uint32_t nvert = wcpt::vertex_bound(bv != nullptr, bv ? bv->bytes - ov : 0);
+    const bool reuse = ctx->tri_cache && t.valid && t.vb == vb && t.ib == ib && t.ntri == ntri && t.gen_vb == gv &&
+                       t.gen_ib == gi && gv != kUnknownGeneration && gi != kUnknownGeneration;
+    if (!reuse) {
+        const wcpt::RecordLayout l = wcpt::record_layout(ntri);
+        if (t.cap < l.bytes) {
+            const int grc = grow(ctx, t.mem, t.cap, l.bytes, l.bytes, "hipMalloc(triangle records)");
+            if (grc) return grc;
+        }
+        t.pair_offset = l.pair_offset;
+        HIP_TRY(ctx, wcpt::launch_build_tri_records(reinterpret_cast<const uint32_t*>(ib), reinterpret_cast<const float*>(vb),
+                                                    ntri, nvert, t.mem, static_cast<char*>(t.mem) + l.pair_offset,
+                                                    ctx->stream), "build_tri_records");
+        t.vb = vb;
+        t.ib = ib;
+        t.gen_vb = gv;
+        t.gen_ib = gi;
+        t.ntri = ntri;
+        t.valid = true;
+        t.build_id++;
+    }
+    const uint64_t nodes = wcpt::bvh_node_count(bb != nullptr, bb ? bb->bytes - ob : 0);
+    if (wcpt::draw_needs_scan(ctx->packed_refs, ctx->tri_cache != 0, nodes, c.indexCount) &&
+        !(t.leaves_valid && t.bvh == c.bvhBuffer && t.gen_bvh == bb->generation && t.bvh_nodes == nodes && t.bvh_ntri == ntri)) {
+        if (!ctx->d_scan) HIP_TRY(ctx, hipMalloc(&ctx->d_scan, sizeof(uint32_t)), "hipMalloc(leaf scan flag)");
+        HIP_TRY(ctx, wcpt::launch_scan_leaf_counts(reinterpret_cast<const void*>(c.bvhBuffer), (uint32_t)nodes, ntri,
+                                                   ctx->d_scan, ctx->stream), "scan_leaf_counts");
+        uint32_t lf = wcpt::kLeafScanUnknown;
+        HIP_TRY(ctx, hipMemcpyAsync(&lf, ctx->d_scan, sizeof(lf), hipMemcpyDeviceToHost, ctx->stream),
+                "hipMemcpyAsync(leaf scan flag)");
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(leaf scan flag)");
+        t.bvh = c.bvhBuffer;
+        t.gen_bvh = bb->generation;
+        t.bvh_nodes = nodes;
+        t.bvh_ntri = ntri;
+        t.leaf_flags = lf;
+        t.leaves_valid = true;
+    }
+    const wcpt::DrawWords w = wcpt::draw_words(ctx->packed_refs, ctx->tri_cache != 0, nodes, c.indexCount, t.leaf_flags,
+                                               ctx->mk_tiny_tree, nvert);
+    const uint64_t addr = reinterpret_cast<uint64_t>(t.mem);
+    table_dirty |= set_table_word(ctx, d, wcpt::kTriWordSingles, addr);
+    table_dirty |= set_table_word(ctx, d, wcpt::kTriWordPairs, addr + t.pair_offset);
+    table_dirty |= set_table_word(ctx, d, wcpt::kTriWordCount, w.word2);
+    table_dirty |= set_table_word(ctx, d, wcpt::kTriWordFlags, w.flags);
+    sums.tris_all += ntri;
+    sums.tris_max = std::max<uint64_t>(sums.tris_max, ntri);
+    sums.leaves_all += wcpt::leaf_estimate(bb != nullptr, bb ? bb->bytes : 0, ntri);
+    return WCPT_SUCCESS;
+}
+
+/* Draw d's primary-ray records for the camera position `origin`, where the plan wants them: grown to the draw's pair
+ * records, the context stream's copy derived (once per camera position and records build), table word kTriWordPrimary. */
+int prepare_primary(wcpt_context* ctx, uint32_t d, bool want_primary, const uint32_t origin[3], bool& table_dirty)
+{
+    TriRecords& t = ctx->tri[d];
+    uint64_t paddr = 0;
+    if (want_primary && t.ntri > 0) {
+        const uint64_t bytes = wcpt::record_layout(t.ntri).prim_bytes;
+        if (t.pcap < bytes) {
+            t.prim.valid = false;
+            t.prim1.valid = false;
+            const int rc = grow(ctx, t.pmem, t.pcap, bytes, 2 * bytes, "hipMalloc(primary-ray pair records)");
+            if (rc) return rc;
+        }
+        HIP_TRY(ctx, bring_primary_copy(t, t.prim, t.pmem, origin, t.build_id, ctx->stream), "build_primary_pairs");
+        paddr = reinterpret_cast<uint64_t>(t.pmem);
+    }
+    table_dirty |= set_table_word(ctx, d, wcpt::kTriWordPrimary, paddr);
+    return WCPT_SUCCESS;
+}
+
+/* The host image of n draws' table to the device, grown to n draws: two tables, the second for pipe 1, which differs
+ * only in kTriWordPrimary, pipe 1's copy of the primary-ray records. Blocks the host (the image is host memory). */
+int upload_table(wcpt_context* ctx, uint32_t n, bool table_dirty)
+{
+    constexpr uint64_t W = wcpt::kTriTableWords;
+    if (ctx->tri_table_cap < n) {
+        const int rc = grow(ctx, ctx->d_tri_table, ctx->tri_table_cap, n, 2 * W * n * sizeof(uint64_t),
+                            "hipMalloc(triangle record table)");
+        if (rc) return rc;
+        table_dirty = true;
+    }
+    if (!table_dirty) return WCPT_SUCCESS;
+    const uint64_t second = W * ctx->tri_table_cap;
+    std::vector<uint64_t> both(2 * second, 0);
+    std::copy(ctx->tri_table.begin(), ctx->tri_table.begin() + W * n, both.begin());
+    std::copy(ctx->tri_table.begin(), ctx->tri_table.begin() + W * n, both.begin() + second);
+    for (uint32_t d = 0; d < n; d++)
+        if (ctx->tri_table[W * d + wcpt::kTriWordPrimary])
+            both[second + W * d + wcpt::kTriWordPrimary] = reinterpret_cast<uint64_t>(ctx->tri[d].pmem1());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tri_table, both.data(), both.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
+                                ctx->stream), "hipMemcpyAsync(triangle record table)");
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(triangle record table)");
+    return WCPT_SUCCESS;
+}
+
+/* Derive (or reuse) the triangle records of every draw command, point a.tri_records at their table and choose what
+ * the frame runs (frame_prep.h frame_plan). */
 int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t draws, wcpt::LaunchArgs& a)
 {
     const uint32_t n = sd.drawCommandCount;
-    a.tri_records = nullptr;
-    a.wf_fast = false;
-    a.tiny_tree = false;
     if (n == 0) {
-        /* WCPT_KERNEL_AUTO with no draws: the megakernel (the rule below); an explicit choice stands */
-        ctx->kernel_run = ctx->kernel != WCPT_KERNEL_AUTO ? ctx->kernel : WCPT_KERNEL_MEGAKERNEL;
+        apply_plan(ctx, wcpt::frame_plan(0, 0, 0, 0, 0, 0, ctx->pair_records, ctx->kernel), 0, a);
         return WCPT_SUCCESS;
     }
+    uint32_t origin[3];
+    std::memcpy(origin, sd.position, sizeof(origin));
     const bool handoff = ctx->handoff_valid && ctx->handoff_draws == draws && ctx->handoff.size() == n;
     ctx->handoff_valid = false;
     wcpt_context::PrepCache& pc = ctx->prep;
-    if (!handoff && pc.valid && pc.gen == ctx->generation && pc.draws == draws && pc.n == n &&
-        std::memcmp(pc.origin, sd.position, sizeof(pc.origin)) == 0) {
-        a.pair_records = pc.pair_records;
-        a.wf_fast = pc.wf_fast;
-        a.tiny_tree = pc.tiny_tree;
-        a.triangles = pc.triangles;
-        ctx->kernel_run = pc.kernel_run;
-        a.tri_records = ctx->d_tri_table;
-        set_pipe1_records(ctx, n, a);
-        ctx->prep_missed = false;
-        return WCPT_SUCCESS;
-    }
-    /* Only the camera moved (an editor drag, bench.py --camera orbit): the primary-ray records are derived again for
-     * the new position -- the context stream's copy here, behind that stream's frames; pipe 1's copy on its own stream
-     * before its launch (prep_pipe1) -- and nothing else changes, so the frame overlap goes on. */
     if (!handoff && pc.valid && pc.gen == ctx->generation && pc.draws == draws && pc.n == n) {
-        uint32_t origin[3];
-        std::memcpy(origin, sd.position, sizeof(origin));
-        if (ctx->prim_records) {
-            for (uint32_t d = 0; d < n; d++) {
-                TriRecords& t = ctx->tri[d];
-                if (!t.pvalid || t.ntri == 0) continue;
-                const uint64_t npairs = ((uint64_t)t.ntri + 1u) / 2u;
-                HIP_TRY(ctx, wcpt::launch_build_primary_pairs(static_cast<const char*>(t.mem) + t.pair_offset,
-                                                              (uint32_t)npairs, sd.position[0], sd.position[1],
-                                                              sd.position[2], t.pmem, ctx->stream),
-                        "build_primary_pairs");
-                std::memcpy(t.porigin, origin, sizeof(origin));
+        /* Only the camera moved (an editor drag, bench.py --camera orbit): the primary-ray records are derived again
+         * for the new position -- the context stream's copy here, behind that stream's frames; pipe 1's copy on its own
+         * stream before its launch (prep_pipe1) -- and nothing else changes, so the frame overlap goes on. */
+        if (std::memcmp(pc.origin, origin, sizeof(origin)) != 0) {
+            if (pc.plan.want_primary) {
+                for (uint32_t d = 0; d < n; d++) {
+                    TriRecords& t = ctx->tri[d];
+                    if (!t.prim.valid || t.ntri == 0) continue;
+                    HIP_TRY(ctx, bring_primary_copy(t, t.prim, t.pmem, origin, t.build_id, ctx->stream), "build_primary_pairs");
+                }
             }
+            std::memcpy(pc.origin, origin, sizeof(origin));
         }
-        std::memcpy(pc.origin, origin, sizeof(pc.origin));
-        a.pair_records = pc.pair_records;
-        a.wf_fast = pc.wf_fast;
-        a.tiny_tree = pc.tiny_tree;
-        a.triangles = pc.triangles;
-        ctx->kernel_run = pc.kernel_run;
-        a.tri_records = ctx->d_tri_table;
-        set_pipe1_records(ctx, n, a);
+        apply_plan(ctx, pc.plan, n, a);
         ctx->prep_missed = false;
         return WCPT_SUCCESS;
     }
@@ -431,214 +587,35 @@ int prepare_tri_records(wcpt_context* ctx, const wcpt_scene_data& sd, uint64_t d
      * frame that follows runs on the stream itself (render_common): a camera that moves every frame rebuilds the
      * primary-ray records every frame, and a fork and a join per frame would cost more than the overlap returns */
     ctx->prep_missed = true;
-    int jrc = join_pending(ctx);
-    if (jrc) return jrc;
-    const uint64_t dbytes = (uint64_t)n * sizeof(wcpt_draw_command);
-    uint64_t off = 0;
-    Buffer* db = buffer_at(ctx, draws, off);
-    const bool from_host = ctx->tri_cache && db && shadow_known(*db, off, dbytes);
+    int rc = join_pending(ctx);
+    if (rc) return rc;
     std::vector<wcpt_draw_command> dc;
+    bool from_host = false; /* a frame handed over by render_validate was read from the device: never cached */
     if (handoff) {
         dc.swap(ctx->handoff);
     } else {
-        dc.resize(n);
-        if (from_host) {
-            std::memcpy(dc.data(), db->shadow.data() + off, dbytes);
-        } else {
-            HIP_TRY(ctx, hipMemcpyAsync(dc.data(), reinterpret_cast<const void*>(draws), dbytes, hipMemcpyDeviceToHost,
-                                        ctx->stream), "hipMemcpyAsync(draw commands)");
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(draw commands)");
-        }
+        rc = read_draw_commands(ctx, draws, n, dc, from_host);
+        if (rc) return rc;
     }
     if (ctx->tri.size() < n) ctx->tri.resize(n);
-    constexpr uint64_t W = 5; /* table words per draw (pt_device.h kTriTableWords) */
-    bool table_dirty = ctx->tri_table.size() < W * n;
-    if (table_dirty) ctx->tri_table.resize(W * n, 0);
-    uint64_t tris_all = 0, leaves_all = 0, tris_max = 0;
+    bool table_dirty = ctx->tri_table.size() < (uint64_t)wcpt::kTriTableWords * n;
+    if (table_dirty) ctx->tri_table.resize((uint64_t)wcpt::kTriTableWords * n, 0);
+    PrepSums sums;
     for (uint32_t d = 0; d < n; d++) {
-        TriRecords& t = ctx->tri[d];
-        const uint64_t vb = dc[d].vertexBuffer, ib = dc[d].indexBuffer;
-        uint64_t ov = 0, oi = 0, o = 0;
-        Buffer* bv = buffer_at(ctx, vb, ov);
-        Buffer* bi = buffer_at(ctx, ib, oi);
-        const uint64_t gv = bv ? bv->generation : kUnknownGeneration;
-        const uint64_t gi = bi ? bi->generation : kUnknownGeneration;
-        const uint32_t ntri = dc[d].indexCount / 3u;
-        /* The records are built from indices [0, indexCount) of the draw: an index buffer known to the context must
-         * hold them (the reference's kernel never reads indexCount, but the record build does). Vertex indices are
-         * checked against the vertex buffer's size on the device (an out-of-range index gives a triangle that is
-         * never hit, instead of a read past the buffer). */
-        if (bi && (uint64_t)ntri * 12ull > bi->bytes - oi)
-            return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT,
-                             "draw command %u: indexCount %u exceeds its index buffer (%llu bytes from offset %llu)", d,
-                             dc[d].indexCount, (unsigned long long)(bi->bytes - oi), (unsigned long long)oi);
-        const uint32_t nvert = bv ? (uint32_t)std::min<uint64_t>((bv->bytes - ov) / 12ull, 0xFFFFFFFFull) : 0xFFFFFFFFu;
-        const bool reuse = ctx->tri_cache && t.valid && t.vb == vb && t.ib == ib && t.ntri == ntri && t.gen_vb == gv &&
-                           t.gen_ib == gi && gv != kUnknownGeneration && gi != kUnknownGeneration;
-        if (!reuse) {
-            const uint64_t singles = ((uint64_t)ntri * wcpt::kSingleRecordBytes + 255u) & ~255ull;
-            const uint64_t bytes = singles + ((uint64_t)ntri / 2u + 1u) * wcpt::kPairRecordBytes;
-            if (t.cap < bytes) {
-                if (t.mem) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-                if (t.mem) (void)hipFree(t.mem);
-                t.mem = nullptr;
-                t.cap = 0;
-                HIP_TRY(ctx, hipMalloc(&t.mem, bytes), "hipMalloc(triangle records)");
-                t.cap = bytes;
-            }
-            if (ntri && (vb == 0 || ib == 0))
-                return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "draw command %u: null vertex/index buffer", d);
-            t.pair_offset = singles;
-            HIP_TRY(ctx, wcpt::launch_build_tri_records(reinterpret_cast<const uint32_t*>(ib),
-                                                        reinterpret_cast<const float*>(vb), ntri, nvert, t.mem,
-                                                        static_cast<char*>(t.mem) + singles, ctx->stream),
-                    "build_tri_records");
-            t.vb = vb;
-            t.ib = ib;
-            t.gen_vb = gv;
-            t.gen_ib = gi;
-            t.ntri = ntri;
-            t.valid = true;
-            t.build_id++;
-        }
-        const uint64_t addr = reinterpret_cast<uint64_t>(t.mem);
-        /* stack entries may carry the child's (left, count) when every node index and index position fits in 24
-         * bits (pt_device.h node_ref); unknown BVH size -> node-index entries */
-        Buffer* bb = buffer_at(ctx, dc[d].bvhBuffer, o);
-        const uint64_t nodes = bb ? (bb->bytes - o) / sizeof(wcpt_node) : ~0ull;
-        uint64_t flags = (ctx->packed_refs && nodes < (1ull << 24) && dc[d].indexCount < (1u << 24)) ? 1u : 0u;
-        if (dc[d].indexCount < (1u << 24)) flags |= 2u; /* pt_device.h kTriFlagIndex24 */
-        /* pt_device.h kTriFlagSmallLeaves / kTriFlagLeafRecords: scanned on the device once per BVH buffer generation,
-         * which only the triangle cache tracks; with the cache off the BVH may change behind the runtime on any frame,
-         * and a scan per render would block the host, so the fast leaf layout is simply not used */
-        if ((flags & 1u) && ctx->tri_cache) {
-            const uint64_t gb = bb->generation;
-            if (!(t.leaves_valid && t.bvh == dc[d].bvhBuffer && t.gen_bvh == gb && t.bvh_nodes == nodes &&
-                  t.bvh_ntri == ntri)) {
-                if (!ctx->d_scan) HIP_TRY(ctx, hipMalloc(&ctx->d_scan, sizeof(uint32_t)), "hipMalloc(leaf scan flag)");
-                HIP_TRY(ctx, wcpt::launch_scan_leaf_counts(reinterpret_cast<const void*>(dc[d].bvhBuffer), (uint32_t)nodes,
-                                                           ntri, ctx->d_scan, ctx->stream), "scan_leaf_counts");
-                uint32_t lf = 3;
-                HIP_TRY(ctx, hipMemcpyAsync(&lf, ctx->d_scan, sizeof(lf), hipMemcpyDeviceToHost, ctx->stream),
-                        "hipMemcpyAsync(leaf scan flag)");
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(leaf scan flag)");
-                t.bvh = dc[d].bvhBuffer;
-                t.gen_bvh = gb;
-                t.bvh_nodes = nodes;
-                t.bvh_ntri = ntri;
-                t.leaf_flags = lf;
-                t.leaves_valid = true;
-            }
-            if (!(t.leaf_flags & 1u)) flags |= 4u; /* pt_device.h kTriFlagSmallLeaves */
-            if (!(t.leaf_flags & 2u)) flags |= 8u; /* pt_device.h kTriFlagLeafRecords */
-            /* pt_device.h kTriFlagTinyTree: the scan's own rule (mk_tiny_rule.h), where the option allows the walk */
-            if (wcpt::mk_tiny_enabled(ctx->mk_tiny_tree, (t.leaf_flags & 4u) ? 1u : 0u)) flags |= 16u;
-        }
-        flags |= (uint64_t)nvert << 32;                 /* pt_device.h draw_vertex_count: bounds the index path */
-        /* word 2: ntri, and in its high half the BVH node count when packed refs apply (the buffer-resource node loads
-         * of pt_device.h load_pair_rsrc cover exactly those nodes) */
-        const uint64_t word2 = (uint64_t)ntri | ((flags & 1u) ? (nodes << 32) : 0ull);
-        const uint64_t entry[W] = {addr, addr + t.pair_offset, word2, flags, ctx->tri_table[W * d + 4]};
-        for (uint64_t w = 0; w < W; w++) {
-            if (ctx->tri_table[W * d + w] != entry[w]) {
-                ctx->tri_table[W * d + w] = entry[w];
-                table_dirty = true;
-            }
-        }
-        tris_all += ntri;
-        tris_max = std::max<uint64_t>(tris_max, ntri);
-        leaves_all += bb ? (bb->bytes / sizeof(wcpt_node) + 1u) / 2u : ntri; /* unknown BVH: assume thin leaves */
+        rc = prepare_draw(ctx, d, dc[d], sums, table_dirty);
+        if (rc) return rc;
     }
-    a.triangles = tris_all;
-    /* the wavefront trace's one-draw fast layout: packed stack refs, 24-bit record offsets, buffer-resource node loads */
-    a.wf_fast = n == 1 && (ctx->tri_table[3] & 15u) == 15u && (ctx->tri_table[2] >> 32) > 0;
-    a.tiny_tree = n == 1 && (ctx->tri_table[3] & 16u) != 0u;
-    /* pair leaves address a draw's pair records with 32-bit byte offsets (pt_device.h load_pair_at) */
-    a.pair_records = tris_max <= kPairMaxTriangles &&
-                     (ctx->pair_records == 1 ||
-                      (ctx->pair_records < 0 && leaves_all > 0 && (double)tris_all >= kPairMinTrianglesPerLeaf * leaves_all));
-    /* WCPT_KERNEL_AUTO: the megakernel where leaves hold several triangles (its pair loops and scalar-cache leaves pay),
-     * the wavefront kernel on thin leaves (Cornell 0.37 / mushroom 1.22 ms megakernel against 2.0 ms wavefront on the
-     * mushroom; the atrium 4.8 ms wavefront against 9.8 ms megakernel) */
-    ctx->kernel_run = ctx->kernel != WCPT_KERNEL_AUTO ? ctx->kernel
-                                                      : (a.pair_records || n == 0 ? WCPT_KERNEL_MEGAKERNEL : WCPT_KERNEL_WAVEFRONT);
-    /* primary-ray pair records (megakernel with pair records): derived once per camera position and records build */
-    const bool want_primary = a.pair_records && ctx->kernel_run == WCPT_KERNEL_MEGAKERNEL;
-    uint32_t origin[3];
-    std::memcpy(origin, sd.position, sizeof(origin));
+    const wcpt::FramePlan plan =
+        wcpt::frame_plan(n, ctx->tri_table[wcpt::kTriWordCount], ctx->tri_table[wcpt::kTriWordFlags], sums.tris_all,
+                         sums.leaves_all, sums.tris_max, ctx->pair_records, ctx->kernel);
     for (uint32_t d = 0; d < n; d++) {
-        TriRecords& t = ctx->tri[d];
-        uint64_t paddr = 0;
-        if (want_primary && t.ntri > 0) {
-            const uint64_t npairs = ((uint64_t)t.ntri + 1u) / 2u; /* the pair records build_tri_records writes */
-            const uint64_t bytes = npairs * wcpt::kPrimPairRecordBytes;
-            const bool fresh = t.pvalid && t.pbuild == t.build_id && std::memcmp(t.porigin, origin, sizeof(origin)) == 0;
-            if (!fresh) {
-                if (t.pcap < bytes) {
-                    if (t.pmem) {
-                        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-                        (void)hipFree(t.pmem);
-                    }
-                    t.pmem = nullptr;
-                    t.pcap = 0;
-                    t.pvalid = false;
-                    t.pvalid1 = false;
-                    HIP_TRY(ctx, hipMalloc(&t.pmem, 2 * bytes), "hipMalloc(primary-ray pair records)");
-                    t.pcap = bytes;
-                }
-                HIP_TRY(ctx, wcpt::launch_build_primary_pairs(static_cast<const char*>(t.mem) + t.pair_offset,
-                                                              (uint32_t)npairs, sd.position[0], sd.position[1],
-                                                              sd.position[2], t.pmem, ctx->stream),
-                        "build_primary_pairs");
-                t.pvalid = true;
-                t.pbuild = t.build_id;
-                std::memcpy(t.porigin, origin, sizeof(origin));
-            }
-            paddr = reinterpret_cast<uint64_t>(t.pmem);
-        }
-        if (ctx->tri_table[W * d + 4] != paddr) {
-            ctx->tri_table[W * d + 4] = paddr;
-            table_dirty = true;
-        }
+        rc = prepare_primary(ctx, d, plan.want_primary, origin, table_dirty);
+        if (rc) return rc;
     }
-    if (ctx->tri_table_cap < n) {
-        if (ctx->d_tri_table) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-            (void)hipFree(ctx->d_tri_table);
-        }
-        ctx->d_tri_table = nullptr;
-        ctx->tri_table_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_tri_table, 2 * W * n * sizeof(uint64_t)), "hipMalloc(triangle record table)");
-        ctx->tri_table_cap = n;
-        table_dirty = true;
-    }
-    if (table_dirty) {
-        /* both tables: the second differs only in word 4, pipe 1's copy of the primary-ray records */
-        std::vector<uint64_t> both(2 * W * ctx->tri_table_cap, 0);
-        std::copy(ctx->tri_table.begin(), ctx->tri_table.begin() + W * n, both.begin());
-        std::copy(ctx->tri_table.begin(), ctx->tri_table.begin() + W * n, both.begin() + W * ctx->tri_table_cap);
-        for (uint32_t d = 0; d < n; d++)
-            if (ctx->tri_table[W * d + 4])
-                both[W * ctx->tri_table_cap + W * d + 4] = reinterpret_cast<uint64_t>(ctx->tri[d].pmem1());
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_tri_table, both.data(), both.size() * sizeof(uint64_t),
-                                    hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync(triangle record table)");
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(triangle record table)");
-    }
-    ctx->prim_records = want_primary;
-    a.tri_records = ctx->d_tri_table;
-    set_pipe1_records(ctx, n, a);
-    if (from_host && !handoff) {
-        pc.valid = true;
-        pc.gen = ctx->generation;
-        pc.draws = draws;
-        pc.n = n;
-        std::memcpy(pc.origin, sd.position, sizeof(pc.origin));
-        pc.pair_records = a.pair_records;
-        pc.wf_fast = a.wf_fast;
-        pc.tiny_tree = a.tiny_tree;
-        pc.triangles = a.triangles;
-        pc.kernel_run = ctx->kernel_run;
-    }
+    rc = upload_table(ctx, n, table_dirty);
+    if (rc) return rc;
+    apply_plan(ctx, plan, n, a);
+    if (from_host) pc = {true, ctx->generation, draws, n, {origin[0], origin[1], origin[2]}, plan};
     return WCPT_SUCCESS;
 }
 
@@ -822,9 +799,6 @@ void render_abandon(wcpt_context* ctx)
     if (ctx) ctx->handoff_valid = false;
 }
 
-/* Every check wcpt_render would make before it launches anything, with no launch: the argument checks and, per draw
- * command, the index-count bound of the record build (prepare_tri_records). A group validates all its ranks first, so
- * that an argument error cannot leave some ranks a frame ahead of the others. */
 void set_overlap_suppressed(wcpt_context* ctx, bool on)
 {
     if (ctx) ctx->overlap_suppressed = on;
@@ -842,6 +816,9 @@ int context_frame_streams(wcpt_context* ctx, hipStream_t* out, int cap)
     return n;
 }
 
+/* Every check wcpt_render would make before it launches anything, with no launch: the argument checks and, per draw
+ * command, the checks of the record build (check_draw). A group validates all its ranks first, so
+ * that an argument error cannot leave some ranks a frame ahead of the others. */
 int render_validate(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t materials, uint64_t spheres,
                     uint64_t draws)
 {
@@ -855,33 +832,17 @@ int render_validate(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t ma
     wcpt_context::ValidCache& vc = ctx->validated;
     if (vc.valid && vc.gen == ctx->generation && vc.draws == draws && vc.n == n) return WCPT_SUCCESS;
     vc.valid = false;
-    const uint64_t dbytes = (uint64_t)n * sizeof(wcpt_draw_command);
-    uint64_t off = 0;
-    Buffer* db = buffer_at(ctx, draws, off);
-    const bool from_host = ctx->tri_cache && db && shadow_known(*db, off, dbytes);
+    /* draw commands read from the device (the application may write them behind the runtime) are handed to the render
+     * that follows (prepare_tri_records), so a frame reads them once */
     std::vector<wcpt_draw_command>& dc = ctx->handoff;
-    dc.resize(n);
-    if (from_host) {
-        std::memcpy(dc.data(), db->shadow.data() + off, dbytes);
-    } else {
-        /* read from the device (the application may write draw commands behind the runtime); the render that follows
-         * takes these (prepare_tri_records), so a frame reads them once */
-        rc = join_pending(ctx);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(dc.data(), reinterpret_cast<const void*>(draws), dbytes, hipMemcpyDeviceToHost,
-                                    ctx->stream), "hipMemcpyAsync(draw commands)");
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(draw commands)");
-    }
+    bool from_host = false;
+    rc = read_draw_commands(ctx, draws, n, dc, from_host);
+    if (rc) return rc;
     for (uint32_t d = 0; d < n; d++) {
-        const uint32_t ntri = dc[d].indexCount / 3u;
         uint64_t oi = 0;
-        Buffer* bi = buffer_at(ctx, dc[d].indexBuffer, oi);
-        if (bi && (uint64_t)ntri * 12ull > bi->bytes - oi)
-            return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT,
-                             "draw command %u: indexCount %u exceeds its index buffer (%llu bytes from offset %llu)", d,
-                             dc[d].indexCount, (unsigned long long)(bi->bytes - oi), (unsigned long long)oi);
-        if (ntri && (dc[d].vertexBuffer == 0 || dc[d].indexBuffer == 0))
-            return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "draw command %u: null vertex/index buffer", d);
+        const Buffer* bi = buffer_at(ctx, dc[d].indexBuffer, oi);
+        rc = check_draw(ctx, d, dc[d], bi, oi);
+        if (rc) return rc;
     }
     if (from_host) {
         vc.valid = true;
