@@ -423,6 +423,42 @@ int      wcpt_image_upload(wcpt_context* ctx, const float* src, uint64_t bytes);
 #define WCPT_COMPOSITE_RGBA8   1
 int      wcpt_composite(wcpt_context* ctx, uint64_t dst, int format);
 
+/* ---- bloom for the display step (bloom.comp, composite.comp:44-45). Added under ABI 4. ----------------- */
+/* The reference's bloom.comp builds a glow around whatever exceeds `threshold` (soft knee `knee`) in a pyramid of at
+ * most `levels` levels below the frame, and composite.comp adds it before gamma and the tonemap when its Bloom flag is
+ * set. The reference's host dispatches neither, so the chain of the four modes is fixed here: level l of a width x
+ * height frame has max(1, width >> (l + 1)) x max(1, height >> (l + 1)) texels; `levels` is clipped to
+ * 1 + floor(log2(min(w_0, h_0))); prefilter the image into level 0, downsample level by level, upsample back adding
+ * each level, and add the sampled level 0 to the image in the display step. The sampler (linear, clamp to edge), GLSL's
+ * min / max for NaN and the order of every sum are defined in csrc/wcpt_bloom.h; DESIGN.md section 8 has the protocol.
+ * Callers' defaults: threshold 1.0, knee 0.1, levels 6. */
+typedef struct wcpt_bloom_params {
+    float    threshold;
+    float    knee;     /* finite, > 0 */
+    uint32_t levels;   /* 2..12 requested; fewer are built on a small frame */
+    uint32_t _pad;
+} wcpt_bloom_params;
+/* Host only: the clipped level count and each level's size (`w` and `h` are arrays of 16). A request outside 2..12 or
+ * a frame that admits fewer than 2 levels (its half-resolution base is below 2 texels in width or height) returns
+ * WCPT_ERROR_INVALID_ARGUMENT and writes nothing. */
+int      wcpt_bloom_levels(uint32_t width, uint32_t height, uint32_t requested, uint32_t* levels, uint32_t* w,
+                           uint32_t* h);
+/* wcpt_composite with the Bloom branch taken: asynchronous on the context's stream, same `dst` and `format`. It reads
+ * the accumulation image and never writes it; both pyramids are the context's (allocated by the first call, laid out
+ * again when the screen size changes, freed by wcpt_destroy). Like wcpt_composite it first orders the stream after both
+ * frame-overlap pipes, keeps the primary cache and the frame preparation, always runs exact and leaves wcpt_last_arith
+ * alone. WCPT_ERROR_INVALID_ARGUMENT, with nothing written or launched: a null `p`, a threshold or knee that is not
+ * finite, knee <= 0, levels outside 2..12, a frame that admits fewer than 2 levels, what wcpt_composite refuses about
+ * `dst` and `format`, and a context that does not hold the whole frame (wcpt_set_row_range or wcpt_set_row_stripes in
+ * effect): bloom reads neighbouring rows, and neither halos for row blocks nor a bloom in a group's display payload
+ * (WCPT_PAYLOAD_DISPLAY_RGBA8) are provided. */
+int      wcpt_composite_bloom(wcpt_context* ctx, uint64_t dst, int format, const wcpt_bloom_params* p);
+/* The same result computed on the CPU by the same arithmetic (csrc/wcpt_bloom.h) from a float4 image of width x height
+ * pixels: RGBA32F into `out_rgba32f` and RGBA8 into `out_rgba8`; either may be NULL. No GPU needed. Refuses as
+ * wcpt_composite_bloom does (and a null image), writing nothing. */
+int      wcpt_bloom_host(const float* rgba, uint32_t width, uint32_t height, const wcpt_bloom_params* p,
+                         float* out_rgba32f, uint8_t* out_rgba8);
+
 /* ---- dispatch ---------------------------------------------------------------------------------------- */
 /* The push block of pathTracer.comp:90-95 minus `sdp`: SceneData travels by value. Asynchronous on the
  * context's stream; the caller owns renderedFramesCount sequencing (PathTracingRenderer.jai:423). */

@@ -213,6 +213,13 @@ hipError_t launch_build_tri_records(const uint32_t* indices, const float* vertic
                                     uint32_t vertex_count, void* singles, void* pairs, hipStream_t stream);
 /* composite.comp (pt_composite.hip): gamma + PBR Neutral over `pixels` float4 texels into rgba32f or RGBA8 */
 hipError_t launch_composite(const float4* img, uint64_t pixels, void* dst, bool rgba8, int cus, hipStream_t stream);
+/* bloom.comp + composite.comp with Bloom set (pt_bloom.hip; the chain of wcpt_bloom.h): the `levels` levels of (lw[l],
+ * lh[l]) texels are built in the pyramids `down` and `up` (bloom_pyramid_texels float4 each), then the width x height
+ * image `img` plus the sampled up[0] goes through the display step into rgba32f or RGBA8 at `dst`. 2 * levels launches. */
+uint64_t bloom_pyramid_texels(uint32_t levels, const uint32_t* lw, const uint32_t* lh);
+hipError_t launch_composite_bloom(const float4* img, uint32_t width, uint32_t height, float threshold, float knee,
+                                  uint32_t levels, const uint32_t* lw, const uint32_t* lh, float4* down, float4* up, void* dst,
+                                  bool rgba8, hipStream_t stream);
 /* overlap: WCPT_OPTION_FRAME_OVERLAP as the runtime allows it for this render (0 off, 1 auto, 2 on whenever the tiles
  * are cost-ordered); with 0 a pending overlap is joined first and the frame runs on `stream` */
 hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkState& mk, hipStream_t stream,

@@ -5,7 +5,7 @@
  * (pt_composite.hip) and the CPU oracle (oracle/pt_oracle.c), so both compute the identical binary32 sequence
  * (compiled with -ffp-contract=off). GLSL leaves pow's precision to the driver ("inherited from exp2 and log2");
  * here pow(x, y) = exp(y * log(x)) with the deterministic log/exp of wcpt_libm.h. The bloom input of
- * composite.comp:44-45 is never dispatched by the reference host and is not part of this step.
+ * composite.comp:44-45 is added in front of this step by wcpt_bloom.h (wcpt_composite_bloom).
  */
 #ifndef WCPT_COMPOSITE_H
 #define WCPT_COMPOSITE_H

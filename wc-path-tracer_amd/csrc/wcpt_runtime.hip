@@ -19,6 +19,7 @@
 
 #include "../../include/wcpt.h"
 #include "pt_kernels.h"
+#include "wcpt_bloom.h"
 
 namespace {
 
@@ -139,6 +140,8 @@ struct wcpt_context {
     wcpt::MkState mk;                  /* megakernel launch state (CU count, cost-ordered tiles) */
     uint32_t* d_scratch = nullptr;
     uint32_t* d_scan = nullptr;        /* leaf-count scan flag (prepare_tri_records) */
+    float4* d_bloom = nullptr;         /* wcpt_composite_bloom: the down pyramid, then the up pyramid (on first use) */
+    uint64_t bloom_bytes = 0;
     uint64_t scratch_bytes = 0;
     int kernel = WCPT_KERNEL_MEGAKERNEL;
     int kernel_run = WCPT_KERNEL_MEGAKERNEL; /* the variant the current/last render runs (WCPT_KERNEL_AUTO resolved) */
@@ -983,6 +986,7 @@ int wcpt_destroy(wcpt_context* ctx)
     if (ctx->d_tri_table) (void)hipFree(ctx->d_tri_table);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_scan) (void)hipFree(ctx->d_scan);
+    if (ctx->d_bloom) (void)hipFree(ctx->d_bloom);
     for (auto& p : ctx->events) {
         (void)hipEventDestroy(p.first);
         (void)hipEventDestroy(p.second);
@@ -1377,10 +1381,12 @@ int wcpt_readback(wcpt_context* ctx, float* dst, uint64_t bytes)
     return read_status(ctx);
 }
 
-int wcpt_composite(wcpt_context* ctx, uint64_t dst, int format)
+namespace {
+
+/* What wcpt_composite and wcpt_composite_bloom check about their output: the image exists, the format is one of the
+ * two, and a destination inside a context buffer holds the frame's bytes. */
+int check_composite_target(wcpt_context* ctx, uint64_t dst, int format)
 {
-    int rc = bind(ctx);
-    if (rc) return rc;
     if (!ctx->image) return set_error(ctx, WCPT_ERROR_NO_SCREEN, "no output image");
     if (format != WCPT_COMPOSITE_RGBA32F && format != WCPT_COMPOSITE_RGBA8)
         return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "composite format %d", format);
@@ -1392,11 +1398,58 @@ int wcpt_composite(wcpt_context* ctx, uint64_t dst, int format)
     if (b && off + need > b->bytes)
         return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "composite destination holds %llu bytes, %llu needed",
                          (unsigned long long)(b->bytes - off), (unsigned long long)need);
+    return WCPT_SUCCESS;
+}
+
+} // namespace
+
+int wcpt_composite(wcpt_context* ctx, uint64_t dst, int format)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    rc = check_composite_target(ctx, dst, format);
+    if (rc) return rc;
+    const uint64_t pixels = (uint64_t)ctx->width * ctx->rows;
     int dev = 0, cus = 0;
     HIP_TRY(ctx, hipGetDevice(&dev), "hipGetDevice");
     HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "hipDeviceGetAttribute");
     HIP_TRY(ctx, wcpt::launch_composite(ctx->image, pixels, reinterpret_cast<void*>(dst), format == WCPT_COMPOSITE_RGBA8,
                                         cus, ctx->stream), "composite launch");
+    return WCPT_SUCCESS;
+}
+
+int wcpt_composite_bloom(wcpt_context* ctx, uint64_t dst, int format, const wcpt_bloom_params* p)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    rc = check_composite_target(ctx, dst, format);
+    if (rc) return rc;
+    if (!p) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "null bloom parameters");
+    if (!wcpt_bloom_curve_ok(p->threshold, p->knee))
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bloom threshold %g, knee %g (finite, knee > 0)", (double)p->threshold,
+                         (double)p->knee);
+    if (ctx->sharded)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bloom needs the whole frame: the context holds %u of %u rows",
+                         ctx->rows, ctx->height);
+    uint32_t lw[WCPT_BLOOM_MAX_LEVELS], lh[WCPT_BLOOM_MAX_LEVELS];
+    const uint32_t levels = wcpt_bloom_plan(ctx->width, ctx->height, p->levels, lw, lh);
+    if (levels == 0)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bloom of %u levels (2..12) on a %ux%u frame (2 levels need 4x4)",
+                         p->levels, ctx->width, ctx->height);
+    /* both pyramids in one allocation, the down levels first; every level is written before it is read in each call, so
+     * a new screen size only moves the levels */
+    const uint64_t texels = wcpt::bloom_pyramid_texels(levels, lw, lh);
+    if (2ull * texels * sizeof(float4) > ctx->bloom_bytes) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize(bloom pyramids)");
+        if (ctx->d_bloom) (void)hipFree(ctx->d_bloom);
+        ctx->d_bloom = nullptr;
+        ctx->bloom_bytes = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_bloom, 2ull * texels * sizeof(float4)), "hipMalloc(bloom pyramids)");
+        ctx->bloom_bytes = 2ull * texels * sizeof(float4);
+    }
+    HIP_TRY(ctx, wcpt::launch_composite_bloom(ctx->image, ctx->width, ctx->height, p->threshold, p->knee, levels, lw, lh,
+                                              ctx->d_bloom, ctx->d_bloom + texels, reinterpret_cast<void*>(dst),
+                                              format == WCPT_COMPOSITE_RGBA8, ctx->stream), "bloom composite launch");
     return WCPT_SUCCESS;
 }
 

@@ -5,6 +5,7 @@
  *   wcpt_bvh_build      <- src/PathTracingRenderer.jai:147-217 (UpdateNodeBounds / Subdivide), :228-232
  *   wcpt_camera_update  <- src/PathTracingRenderer.jai:22-36   (Camera Update)
  *   wcpt_scene_generate "default" <- src/PathTracingRenderer.jai:322-339 (Init's materials and spheres)
+ *   wcpt_bloom_host     <- src/shaders/bloom.comp, composite.comp:44-45 through csrc/wcpt_bloom.h (the device's arithmetic)
  *
  * No GPU is needed for anything in this file.
  */
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "../../include/wcpt.h"
+#include "../csrc/wcpt_bloom.h"
 
 namespace {
 
@@ -824,6 +826,68 @@ int scene_atrium(uint32_t seed, wcpt_scene* out)
     return fill_scene(out, mb, mats, sph, make_camera(-11.0f, 2.2f, 0.0f, 0.0f, 6.0f, 70.0f));
 }
 
+/* ------------------------------------------------------------------------------------------------ */
+/* Bloom: the chain of csrc/wcpt_bloom.h over float4 arrays                                         */
+
+struct HostTexture {
+    const float* texels; /* float4 per texel */
+    int w;
+    void operator()(int x, int y, float rgb[3]) const
+    {
+        const float* t = texels + 4 * ((size_t)y * (size_t)w + (size_t)x);
+        rgb[0] = t[0];
+        rgb[1] = t[1];
+        rgb[2] = t[2];
+    }
+};
+
+void bloom_host(const float* rgba, uint32_t width, uint32_t height, const wcpt_bloom_curve& curve, uint32_t levels,
+                const uint32_t* lw, const uint32_t* lh, float* out32, uint8_t* out8)
+{
+    const wcpt_bloom_size frame = wcpt_bloom_make_size(width, height);
+    std::vector<wcpt_bloom_size> size(levels);
+    std::vector<std::vector<float>> down(levels), up(levels - 1);
+    for (uint32_t l = 0; l < levels; l++) {
+        size[l] = wcpt_bloom_make_size(lw[l], lh[l]);
+        down[l].assign((size_t)lw[l] * lh[l] * 4, 1.0f); /* alpha 1 (bloom.comp:147) */
+        if (l + 1 < levels) up[l].assign((size_t)lw[l] * lh[l] * 4, 1.0f);
+    }
+    for (uint32_t l = 0; l < levels; l++) { /* MODE_PREFILTER, then MODE_DOWNSAMPLE */
+        const HostTexture src{l ? down[l - 1].data() : rgba, l ? size[l - 1].w : frame.w};
+        const wcpt_bloom_size& ss = l ? size[l - 1] : frame;
+        for (int y = 0; y < size[l].h; y++)
+            for (int x = 0; x < size[l].w; x++) {
+                float* o = &down[l][4 * ((size_t)y * size[l].w + x)];
+                if (l == 0)
+                    wcpt_bloom_prefilter_texel(src, ss, size[l], x, y, curve, o);
+                else
+                    wcpt_bloom_downsample_texel(src, ss, size[l], x, y, o);
+            }
+    }
+    for (uint32_t l = levels - 1; l-- > 0;) { /* MODE_UPSAMPLE_FIRST, then MODE_UPSAMPLE */
+        const HostTexture below{l + 2 == levels ? down[l + 1].data() : up[l + 1].data(), size[l + 1].w};
+        for (int y = 0; y < size[l].h; y++)
+            for (int x = 0; x < size[l].w; x++) {
+                const size_t i = 4 * ((size_t)y * size[l].w + x);
+                wcpt_bloom_upsample_texel(below, size[l + 1], size[l], x, y, &down[l][i], &up[l][i]);
+            }
+    }
+    const HostTexture bloom{up[0].data(), size[0].w};
+    for (int y = 0; y < frame.h; y++)
+        for (int x = 0; x < frame.w; x++) {
+            const size_t i = (size_t)y * frame.w + x;
+            float o[4];
+            wcpt_bloom_display_texel(bloom, size[0], frame, x, y, rgba + 4 * i, o);
+            if (out32) memcpy(out32 + 4 * i, o, sizeof(o));
+            if (out8) {
+                out8[4 * i + 0] = wcpt_unorm8(o[0]);
+                out8[4 * i + 1] = wcpt_unorm8(o[1]);
+                out8[4 * i + 2] = wcpt_unorm8(o[2]);
+                out8[4 * i + 3] = 255;
+            }
+        }
+}
+
 } // namespace
 
 extern "C" {
@@ -952,5 +1016,32 @@ int wcpt_mesh_to_obj(const wcpt_mesh* mesh, char** out_text, uint64_t* out_lengt
 }
 
 void wcpt_string_free(char* text) { free(text); }
+
+int wcpt_bloom_levels(uint32_t width, uint32_t height, uint32_t requested, uint32_t* levels, uint32_t* w, uint32_t* h)
+{
+    if (!levels || !w || !h) return WCPT_ERROR_INVALID_ARGUMENT;
+    uint32_t lw[WCPT_BLOOM_MAX_LEVELS], lh[WCPT_BLOOM_MAX_LEVELS];
+    const uint32_t n = wcpt_bloom_plan(width, height, requested, lw, lh);
+    if (n == 0) return WCPT_ERROR_INVALID_ARGUMENT;
+    *levels = n;
+    memcpy(w, lw, n * sizeof(uint32_t));
+    memcpy(h, lh, n * sizeof(uint32_t));
+    return WCPT_SUCCESS;
+}
+
+int wcpt_bloom_host(const float* rgba, uint32_t width, uint32_t height, const wcpt_bloom_params* p, float* out_rgba32f,
+                    uint8_t* out_rgba8)
+{
+    if (!rgba || !p || !wcpt_bloom_curve_ok(p->threshold, p->knee)) return WCPT_ERROR_INVALID_ARGUMENT;
+    uint32_t lw[WCPT_BLOOM_MAX_LEVELS], lh[WCPT_BLOOM_MAX_LEVELS];
+    const uint32_t n = wcpt_bloom_plan(width, height, p->levels, lw, lh);
+    if (n == 0) return WCPT_ERROR_INVALID_ARGUMENT;
+    try {
+        bloom_host(rgba, width, height, wcpt_bloom_make_curve(p->threshold, p->knee), n, lw, lh, out_rgba32f, out_rgba8);
+    } catch (...) {
+        return WCPT_ERROR_OUT_OF_HOST_MEMORY;
+    }
+    return WCPT_SUCCESS;
+}
 
 } /* extern "C" */

@@ -3,7 +3,7 @@
 The compute lives in libwcpt.so (hand-written HIP for gfx950 behind the C-ABI of include/wcpt.h); this
 package is the Python host mirror used by tests and the benchmark.
 """
-from ._lib import (COUNTER_FIELDS, DRAW_COMMAND_DTYPE, EXPORTED_SYMBOLS, KERNEL_AUTO, KERNEL_MEGAKERNEL,
+from ._lib import (BloomParams, COUNTER_FIELDS, DRAW_COMMAND_DTYPE, EXPORTED_SYMBOLS, KERNEL_AUTO, KERNEL_MEGAKERNEL,
                    KERNEL_WAVEFRONT, LIB_PATH, MATERIAL_DIELECTRIC, MATERIAL_DTYPE, MATERIAL_METAL, NODE_DTYPE,
                    SCENE_DATA_DTYPE, SPHERE_DTYPE, Camera, WcptError, lib)
 from .renderer import Context, DeviceScene, Editor, Group, PathTracingRenderer, group_unique_id
@@ -15,6 +15,7 @@ __all__ = [
     "KERNEL_WAVEFRONT", "LIB_PATH", "MATERIAL_DIELECTRIC", "MATERIAL_DTYPE", "MATERIAL_METAL", "NODE_DTYPE",
     "SCENE_DATA_DTYPE", "SPHERE_DTYPE", "Camera", "WcptError", "lib", "Context", "DeviceScene",
     "PathTracingRenderer", "Editor", "Group", "group_unique_id", "scene", "device_count", "device_pci_bus_id", "runtime_version", "build_id",
+    "BloomParams", "bloom_levels", "bloom_host",
 ]
 
 
@@ -44,3 +45,29 @@ def runtime_version() -> int:
     v = C.c_int()
     _lib.check(lib.wcpt_runtime_version(C.byref(v)))
     return v.value
+
+
+def bloom_levels(width: int, height: int, requested: int = 6) -> list:
+    """wcpt_bloom_levels: the (w, h) of each level of the bloom pyramid of a width x height frame, `requested` levels
+    clipped to what the frame admits; raises WcptError where wcpt_composite_bloom would refuse."""
+    import ctypes as C
+    n = C.c_uint32()
+    w = (C.c_uint32 * _lib.BLOOM_MAX_LEVELS)()
+    h = (C.c_uint32 * _lib.BLOOM_MAX_LEVELS)()
+    _lib.check(lib.wcpt_bloom_levels(width, height, requested, C.byref(n), w, h))
+    return [(int(w[i]), int(h[i])) for i in range(n.value)]
+
+
+def bloom_host(img, params=None):
+    """wcpt_bloom_host: what Context.composite(dst, bloom=params) stores for the float4 image `img` [H][W][4], computed
+    on the CPU by the same arithmetic (no GPU needed): returns (rgba32f, rgba8)."""
+    import numpy as np
+    a = np.ascontiguousarray(img, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("bloom_host: an image of shape (height, width, 4)")
+    params = BloomParams() if params is None else params
+    out32 = np.empty(a.shape, np.float32)
+    out8 = np.empty(a.shape, np.uint8)
+    import ctypes as C
+    _lib.check(lib.wcpt_bloom_host(_lib.ptr(a), a.shape[1], a.shape[0], C.byref(params), _lib.ptr(out32), _lib.ptr(out8)))
+    return out32, out8

@@ -139,6 +139,17 @@ class GroupInfo(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class BloomParams(C.Structure):
+    """wcpt_bloom_params (include/wcpt.h): the callers' defaults are threshold 1.0, knee 0.1, 6 levels."""
+    _fields_ = [("threshold", C.c_float), ("knee", C.c_float), ("levels", C.c_uint32), ("_pad", C.c_uint32)]
+
+    def __init__(self, threshold: float = 1.0, knee: float = 0.1, levels: int = 6):
+        super().__init__(threshold, knee, levels, 0)
+
+
+BLOOM_MAX_LEVELS = 16  # the arrays of wcpt_bloom_levels
+
+
 class SceneC(C.Structure):
     _fields_ = [("mesh", Mesh), ("materials", C.c_void_p), ("material_count", C.c_uint32),
                 ("spheres", C.c_void_p), ("sphere_count", C.c_uint32), ("camera", Camera)]
@@ -178,6 +189,9 @@ _PROTOTYPES = {
     "wcpt_readback": (_i, [_p, _p, _u64]),
     "wcpt_image_upload": (_i, [_p, _p, _u64]),
     "wcpt_composite": (_i, [_p, _u64, _i]),
+    "wcpt_composite_bloom": (_i, [_p, _u64, _i, C.POINTER(BloomParams)]),
+    "wcpt_bloom_levels": (_i, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "wcpt_bloom_host": (_i, [_p, _u32, _u32, C.POINTER(BloomParams), _p, _p]),
     "wcpt_render": (_i, [_p, _p, _u64, _u64, _u64]),
     "wcpt_sync": (_i, [_p]),
     "wcpt_primary_cache_stats": (_i, [_p, C.POINTER(_u64), C.POINTER(_u64)]),

@@ -152,9 +152,13 @@ class Context:
         self._chk(lib.wcpt_image_upload(self.h, ptr(a), a.nbytes))
 
     # -- dispatch ---------------------------------------------------------------------------------------
-    def composite(self, dst: int, rgba8: bool = False):
-        """composite.comp into device memory at `dst` (asynchronous)."""
-        self._chk(lib.wcpt_composite(self.h, dst, 1 if rgba8 else 0))
+    def composite(self, dst: int, rgba8: bool = False, bloom=None):
+        """composite.comp into device memory at `dst` (asynchronous); with `bloom` (a BloomParams) its Bloom branch is
+        taken: bloom.comp's pyramid of the image is added before gamma and the tonemap (wcpt_composite_bloom)."""
+        if bloom is None:
+            self._chk(lib.wcpt_composite(self.h, dst, 1 if rgba8 else 0))
+        else:
+            self._chk(lib.wcpt_composite_bloom(self.h, dst, 1 if rgba8 else 0, C.byref(bloom)))
 
     def render(self, sd: np.ndarray, materials: int, spheres: int, draws: int):
         sd = np.ascontiguousarray(sd, dtype=SCENE_DATA_DTYPE)
