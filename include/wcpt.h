@@ -677,7 +677,12 @@ int      wcpt_selftest_device(wcpt_context* ctx, int fn, const uint32_t* in, con
  *   fn 7  one path_shade step (not the last segment, a hit)
  *                              in 33: origin, direction, the Hit's p, normal, t, front (1 / 0), one wcpt_material
  *                              (15 words), the rng state, transmittance
- *                              out 10: the next origin, direction, transmittance, the rng state */
+ *                              out 10: the next origin, direction, transmittance, the rng state
+ *   fn 8  the child-pair decision of an interior BVH node and the root cull (child_pair, root_survives; the box test has
+ *         no fast form, so both modes give the same words)
+ *                              in 19: origin, invDirection, the left child's box (min, max), the right child's, rec.t
+ *                              out 6: 1 / 0 left child popped first, left box passed, right box passed; the entry
+ *                              distance t0 of the left box, of the right box; 1 / 0 the left box as a root survives rec.t */
 int      wcpt_selftest_geometry(wcpt_context* ctx, int fn, int arith, const uint32_t* in, uint32_t in_words,
                                 uint32_t* out, uint32_t out_words, uint32_t n);
 

@@ -51,6 +51,8 @@ def _load():
     lib.oracle_random_direction.argtypes = [C.POINTER(C.c_uint32), C.c_void_p]
     lib.oracle_ray_box.restype = None
     lib.oracle_ray_box.argtypes = [C.c_void_p] * 5
+    lib.oracle_child_pair.restype = None
+    lib.oracle_child_pair.argtypes = [C.c_void_p, C.c_void_p]
     lib.oracle_ray_sphere.restype = f
     lib.oracle_ray_sphere.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, f]
     lib.oracle_ray_triangle.restype = f
@@ -109,6 +111,17 @@ def ray_box(o, d, bmin, bmax):
     out = np.zeros(2, np.float32)
     a = [_f3(o), _f3(d), _f3(bmin), _f3(bmax)]
     lib.oracle_ray_box(*[x.ctypes.data for x in a], out.ctypes.data)
+    return out
+
+
+def child_pair(items):
+    """Intersect's child-pair decision and root cull on items[n, 19] (float32; the layout of wcpt_selftest_geometry fn 8):
+    the six output words per item, [n, 6] uint32."""
+    items = np.ascontiguousarray(items, np.float32)
+    assert items.ndim == 2 and items.shape[1] == 19
+    out = np.zeros((len(items), 6), np.uint32)
+    for k in range(len(items)):
+        lib.oracle_child_pair(items[k].ctypes.data, out[k].ctypes.data)
     return out
 
 

@@ -174,6 +174,11 @@ static inline v2 rayBoxIntersect(const Ray* ray, v3 bmin, v3 bmax)
     return r;
 }
 
+/* The traversal's decisions on a box test's (t0, t1), stated once for Intersect and for oracle_child_pair: the cull of a
+ * popped node (:162) and a child's distance for the pop order (:190-191). */
+static inline int boxCulled(v2 t, float recT) { return t.x > t.y || t.y < 0.0f || t.x > recT; }
+static inline float childDist(v2 t) { return (t.x > 0.0f) ? t.x : t.y; }
+
 /* pathTracer.comp:110-119 (only .x is used by the caller, :141) */
 static inline float raySphereIntersectNear(const Ray* ray, v3 position, float radius)
 {
@@ -241,7 +246,7 @@ static HitInfo Intersect(Scene* S, const Ray* ray)
             const wcpt_node* node = &dc->bvh[nodeIdx];
             const v2 bvhT = rayBoxIntersect(ray, ld3(node->min), ld3(node->max));
             S->cnt->node_pops++;
-            if (bvhT.x > bvhT.y || bvhT.y < 0.0f || bvhT.x > rec.t) continue;
+            if (boxCulled(bvhT, rec.t)) continue;
             if (node->triangleCount > 0) {
                 for (uint32_t k = 0; k < node->triangleCount; k += 3) {
                     const uint32_t first = k + node->leftNodeOrTriangleIndex;
@@ -264,8 +269,8 @@ static HitInfo Intersect(Scene* S, const Ray* ray)
                 const wcpt_node* rightNode = &dc->bvh[rightChild];
                 const v2 leftT = rayBoxIntersect(ray, ld3(leftNode->min), ld3(leftNode->max));
                 const v2 rightT = rayBoxIntersect(ray, ld3(rightNode->min), ld3(rightNode->max));
-                const float leftDist = (leftT.x > 0.0f) ? leftT.x : leftT.y;
-                const float rightDist = (rightT.x > 0.0f) ? rightT.x : rightT.y;
+                const float leftDist = childDist(leftT);
+                const float rightDist = childDist(rightT);
                 S->cnt->interior_visits++;
                 if (stackIndex + 2 > 32) ref_overflow = 1;
                 if ((uint64_t)(stackIndex + 2) > S->cnt->ref_stack_max) S->cnt->ref_stack_max = (uint64_t)(stackIndex + 2);
@@ -492,6 +497,23 @@ void oracle_ray_box(const float* o, const float* d, const float* bmin, const flo
     r.origin = ld3(o); r.direction = ld3(d); r.invDirection = sdiv3(1.0f, r.direction);
     v2 t = rayBoxIntersect(&r, ld3(bmin), ld3(bmax));
     out2[0] = t.x; out2[1] = t.y;
+}
+/* One item of the device self-test wcpt_selftest_geometry fn 8 (origin, invDirection, the left and the right child's box
+ * as min, max, rec.t) through Intersect's own decisions: whether the left child is popped first (pushed last), whether each
+ * child survives the part of its pop's cull that does not depend on rec.t (no t0 exceeds +infinity), the bits of each
+ * child's entry distance, and whether the left box as a root survives rec.t. */
+void oracle_child_pair(const float* item, uint32_t* out6)
+{
+    Ray r;
+    r.origin = ld3(item); r.direction = mk3(0.0f, 0.0f, 0.0f); r.invDirection = ld3(item + 3);
+    const v2 leftT = rayBoxIntersect(&r, ld3(item + 6), ld3(item + 9));
+    const v2 rightT = rayBoxIntersect(&r, ld3(item + 12), ld3(item + 15));
+    out6[0] = childDist(leftT) < childDist(rightT);
+    out6[1] = !boxCulled(leftT, INFINITY);
+    out6[2] = !boxCulled(rightT, INFINITY);
+    memcpy(&out6[3], &leftT.x, 4);
+    memcpy(&out6[4], &rightT.x, 4);
+    out6[5] = !boxCulled(leftT, item[18]);
 }
 float oracle_ray_sphere(const float* o, const float* d, const float* c, float radius)
 {

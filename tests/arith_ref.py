@@ -1,5 +1,6 @@
 """binary64 references, derived error bounds, binary32 models and input sets for the composite device functions that
-wcpt_selftest_geometry exposes (wcpt.h: fn 0..7). numpy only; shared by tests/test_arith_ref_cpu.py (which checks the
+wcpt_selftest_geometry exposes (wcpt.h: fn 0..7; fn 8, the traversal's child-pair decision, has no fast form and no bound:
+child_pair_model and child_pair_set at the end). numpy only; shared by tests/test_arith_ref_cpu.py (which checks the
 bounds themselves, without a GPU) and tests/test_gpu_arith_functions.py (which checks the kernels against them).
 
 One text per formula, several arithmetics. Each formula below is written once, in the operation order of pt_device.h,
@@ -48,7 +49,8 @@ U = 2.0 ** -24
 SAFETY = 2.0
 TINY = 2.0 ** -126
 MAX_UNDECIDED = 0.02
-WORDS = {0: (15, 1), 1: (24, 4), 2: (24, 4), 3: (10, 1), 4: (11, 7), 5: (8, 7), 6: (3, 6), 7: (33, 10)}
+WORDS = {0: (15, 1), 1: (24, 4), 2: (24, 4), 3: (10, 1), 4: (11, 7), 5: (8, 7), 6: (3, 6), 7: (33, 10),
+         8: (19, 6)}
 K_BIAS = np.float32(1e-5)
 _ERR = dict(divide="ignore", invalid="ignore", over="ignore", under="ignore")
 
@@ -984,3 +986,124 @@ def all_sets():
         for name, x in sets.items():
             out[fn, name] = x
     return out
+
+
+# ---- fn 8: the child-pair decision and the root cull -------------------------------------------------------------------
+# No arithmetic object here: the box test is the same binary32 operations in both modes, and every output is a decision or
+# a distance that decisions read, so the check is bit for bit (a NaN distance matching any NaN).
+def _ray_box32(o, inv, bmin, bmax):
+    """rayBoxIntersect (pathTracer.comp:97-108, oracle/pt_oracle.c) in binary32: (t0, t1). GLSL min / max are IEEE minNum /
+    maxNum -- a NaN operand gives the other one -- which is np.fmin / np.fmax."""
+    tbot = [(bmin[k] - o[k]) * inv[k] for k in range(3)]
+    ttop = [(bmax[k] - o[k]) * inv[k] for k in range(3)]
+    tmin = [np.fmin(ttop[k], tbot[k]) for k in range(3)]
+    tmax = [np.fmax(ttop[k], tbot[k]) for k in range(3)]
+    t0 = np.fmax(np.fmax(tmin[0], tmin[1]), np.fmax(tmin[0], tmin[2]))
+    t1 = np.fmin(np.fmin(tmax[0], tmax[1]), np.fmin(tmax[0], tmax[2]))
+    assert t0.dtype == np.float32 and t1.dtype == np.float32
+    return t0, t1
+
+
+def child_pair_model(x):
+    """What wcpt_selftest_geometry(8) returns for the items x[n, 19] (float32: origin, invDirection, left box min, max, right
+    box min, max, rec.t), in the oracle's expressions (pt_oracle.c Intersect): left popped first iff leftDist < rightDist
+    with dist = t0 > 0 ? t0 : t1; a box passes unless t0 > t1 || t1 < 0; a root survives unless that or t0 > rec.t. Every
+    comparison with a NaN is false, as in C."""
+    x = np.asarray(x, np.float32)
+    c = lambda k: tuple(x[:, k + i] for i in range(3))                   # noqa: E731
+    with np.errstate(**_ERR):
+        l0, l1 = _ray_box32(c(0), c(3), c(6), c(9))
+        r0, r1 = _ray_box32(c(0), c(3), c(12), c(15))
+        left_dist, right_dist = np.where(l0 > 0, l0, l1), np.where(r0 > 0, r0, r1)
+        culled_l, culled_r = (l0 > l1) | (l1 < 0), (r0 > r1) | (r1 < 0)
+        return _u32(_flag(left_dist < right_dist), _flag(~culled_l), _flag(~culled_r), l0, r0,
+                    _flag(~(culled_l | (l0 > x[:, 18]))))
+
+
+def child_pair_set():
+    """fn 8 items by case, a few dozen of each (a few hundred in all). The one thing left out on purpose: a min or max of
+    two zeros of different sign, whose sign IEEE 754-2008 leaves open (v_min_f32, C's compare-select and numpy differ) and
+    no decision reads; so no finite invDirection meets an origin on a slab plane here (with an infinite one the product is
+    NaN, which is the case that matters)."""
+    rng = np.random.default_rng(410)
+    inf, nan, big = np.float32(np.inf), np.float32(np.nan), np.float32(3.402823466e+38)
+    n = 32
+
+    def boxes(k):
+        lo = rng.uniform(-2, 2, (k, 3))
+        return lo, lo + rng.uniform(0.1, 2, (k, 3))
+
+    def items(k, o=None, d=None, lb=None, rb=None, rt=None):
+        o = rng.uniform(-3, 3, (k, 3)) if o is None else o
+        d = _unit(rng, k) if d is None else d
+        lb, rb = boxes(k) if lb is None else lb, boxes(k) if rb is None else rb
+        rt = 10.0 ** rng.uniform(-1, 1.5, (k, 1)) if rt is None else rt
+        with np.errstate(**_ERR):
+            inv = np.float32(1.0) / np.asarray(d, np.float32)           # 1 / +-0 = +-inf, as rcp3 gives
+        return np.concatenate([np.asarray(o, np.float32), inv, *[np.asarray(v, np.float32) for v in (*lb, *rb)],
+                               np.asarray(rt, np.float32)], axis=1).astype(np.float32)
+
+    def near(lb):
+        """a box that overlaps lb: the same ray mostly meets both, so the pop order is a real decision"""
+        shift = rng.uniform(-0.5, 0.5, lb[0].shape)
+        return lb[0] + shift, lb[1] + shift
+
+    def through(lb, k, d=None):
+        """origins 1 .. 4 behind a point inside the box lb along the direction d (default: random unit vectors)"""
+        p = lb[0] + rng.uniform(0.1, 0.9, (k, 3)) * (lb[1] - lb[0])
+        d = _unit(rng, k) if d is None else d
+        return p - rng.uniform(1, 4, (k, 1)) * d, d
+
+    def hitting(k):
+        lb = boxes(k)
+        return (*through(lb, k), lb, near(lb))
+
+    row = np.arange(n)
+    sets = [items(2 * n), items(2 * n, *hitting(2 * n))]                # random boxes and rays; rays through the left box
+    # invDirection components of +-inf (direction components +-0; a quarter of the items have two): the origin inside the
+    # slab, outside it, and on one of the four planes of the two boxes (0 * inf = NaN for that plane)
+    for where in ("inside", "outside", "plane"):
+        lb = boxes(n)
+        rb = near(lb)
+        d = _unit(rng, n)
+        axis = rng.integers(0, 3, n)
+        d[row, axis] = 0.0 * rng.choice([-1.0, 1.0], n)
+        two = rng.uniform(size=n) < 0.25
+        d[two, (axis[two] + 1) % 3] = 0.0 * rng.choice([-1.0, 1.0], int(two.sum()))
+        o, d = through(lb, n, d)                                        # inside the left box's slab on the zero axes
+        if where == "outside":
+            o[row, axis] += rng.choice([-3.0, 3.0], n)
+        elif where == "plane":
+            planes = np.stack([*lb, *rb])[:, row, axis]                 # left min, left max, right min, right max
+            o[row, axis] = np.float32(planes[rng.integers(0, 4, n), row])   # the binary32 plane itself
+        sets.append(items(n, o, d, lb, rb))
+    # every distance NaN: a box of no extent that holds the origin, and no direction at all (0 * inf on all six planes)
+    o = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
+    flat, zero = (o, o), 0.0 * rng.choice([-1.0, 1.0], (n, 3))
+    sets += [items(n, o, zero, flat, flat), items(n, o, zero, flat, boxes(n)), items(n, o, zero, boxes(n), flat)]
+    lb = boxes(n)
+    sets.append(items(n, *through(lb, n), lb, lb))                      # equal boxes: leftDist == rightDist
+    x = items(n, *hitting(n))
+    x[:, 12:15], x[:, 15:18] = 2 * x[:, 0:3] - x[:, 9:12], 2 * x[:, 0:3] - x[:, 6:9]
+    sets.append(x)                                                      # the right box is the left one mirrored at the origin
+    o, d, lb, rb = hitting(n)
+    sets.append(items(n, o, -d, lb, rb))                                # both boxes behind the ray
+    sets.append(items(n, *through(lb, n, -d), boxes(n), lb))            # the right one alone
+    x = items(n, *hitting(n))
+    with np.errstate(**_ERR):
+        x[:, 18] = _ray_box32(*[tuple(x[:, k + i] for i in range(3)) for k in (0, 3, 6, 9)])[0]
+    sets.append(x)                                                      # rec.t equal to the left box's t0: survives
+    below = x.copy()
+    below[:, 18] = np.nextafter(x[:, 18], -inf)
+    sets.append(below)                                                  # and one ULP below it: culled
+    x = items(n, *hitting(n))
+    x[:, 18] = big
+    x[n // 2:, 18] = inf
+    sets.append(x)                                                      # rec.t = kInfinity (and +inf)
+    x = np.concatenate([items(n), items(n, *hitting(n))])
+    x[np.arange(2 * n), 6 + rng.integers(0, 12, 2 * n)] = nan
+    sets.append(x)                                                      # NaN in a box word
+    x = items(n, *hitting(n))
+    x[row, 6 + rng.integers(0, 12, n)] = rng.choice([-inf, inf], n)
+    sets.append(x)                                                      # an infinite box word
+    return np.concatenate(sets).astype(np.float32)

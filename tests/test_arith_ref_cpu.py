@@ -6,6 +6,7 @@
      ULP down.
   3. At most 2 % of any set is undecided (nearer to a decision threshold than its bound).
   4. The bounds are tight enough to be worth having: six deliberately wrong formulas each violate them on some set.
+  5. The traversal's child-pair decision (fn 8, no bound: bit for bit) as numpy states it is the oracle's C on every item.
 """
 import functools
 
@@ -100,3 +101,23 @@ def test_mutants_are_caught(mutant):
                 caught[name] = int(rep.bad.sum())
         print(f"{mutant} in fn {fn}: violations per set {caught}")
         assert max(caught.values()) > 0, f"{mutant} passes every set of fn {fn}"
+
+
+def test_child_pair_model_is_the_oracles():
+    """arith_ref.child_pair_model against oracle/pt_oracle.c's own box test and Intersect's own decisions
+    (oracle_child_pair) on the items the GPU test uses: every word equal, a NaN distance matching a NaN. The set holds what
+    it claims to: NaN distances, both pop orders, passing and failing boxes, roots that survive and roots that do not."""
+    import oracle
+    x = R.child_pair_set()
+    assert 300 <= len(x) <= 1000 and x.shape[1] == R.WORDS[8][0]
+    got, want = R.child_pair_model(x), oracle.child_pair(x)
+    assert got.shape == want.shape == (len(x), R.WORDS[8][1])
+    both_nan = np.isnan(got.view(np.float32)) & np.isnan(want.view(np.float32))
+    differ = ((got != want) & ~both_nan).any(axis=1)
+    assert not differ.any(), f"{int(differ.sum())} of {len(x)} items differ, first {int(np.flatnonzero(differ)[0])}"
+    t0 = got[:, 3:5].view(np.float32)
+    nan_l, nan_r = np.isnan(t0[:, 0]), np.isnan(t0[:, 1])
+    assert (nan_l & nan_r).any() and (nan_l & ~nan_r).any() and (~nan_l & nan_r).any()
+    for k in (0, 1, 2, 5):
+        assert 0 < got[:, k].sum() < len(x), f"word {k} is the same for every item"
+    assert (t0 == x[:, 18:19]).any() and np.isinf(x[:, 3:6]).any() and np.isnan(x[:, 6:18]).any()

@@ -11,6 +11,10 @@ Fresnel, normalize and the reciprocals, one scatter step of path_shade -- runs a
               where that one is further from its threshold than the bound (arith_ref.check). The bounds come from the
               rounding of the formulas alone; tests/test_arith_ref_cpu.py checks them, and that six wrong formulas break
               them, without a GPU.
+
+The traversal's child-pair decision and root cull (fn 8: child_pair, root_survives, the one definition the megakernel's
+loop and its tiny walk use) have no fast form and no bound: bit for bit the oracle's expressions in numpy
+binary32 (arith_ref.child_pair_model, itself checked against the oracle's C on the CPU), the same in both modes.
 """
 import numpy as np
 import pytest
@@ -41,7 +45,7 @@ def _same_bits(got, want, what):
 
 def test_arguments(gpu_ctx):
     x = np.zeros((4, 15), np.uint32)
-    for fn, arith, iw, ow in ((0, 2, 15, 1), (0, -1, 15, 1), (8, EXACT, 15, 1), (-1, FAST, 15, 1), (0, EXACT, 14, 1),
+    for fn, arith, iw, ow in ((0, 2, 15, 1), (0, -1, 15, 1), (8, EXACT, 15, 1), (9, EXACT, 19, 6), (-1, FAST, 15, 1), (0, EXACT, 14, 1),
                               (0, FAST, 15, 2), (6, FAST, 15, 6)):
         out = np.zeros((4, ow), np.uint32)
         rc = wcpt.lib.wcpt_selftest_geometry(gpu_ctx.h, fn, arith, wcpt.renderer.ptr(x), iw, wcpt.renderer.ptr(out), ow, 4)
@@ -137,3 +141,15 @@ def test_pair_halves_agree(gpu_ctx, name, arith):
     out_ab, out_ba = _run(gpu_ctx, 1, arith, ab), _run(gpu_ctx, 1, arith, ba)
     _same_bits(out_ab[:, [0, 1, 2, 3]], out_ba[:, [1, 0, 3, 2]], "swapped halves")
     assert np.array_equal(out_ab[:, 0], same[:, 0]) and np.array_equal(out_ab[:, 2], same[:, 2])
+
+
+def test_child_pair_decision_bit_for_bit(gpu_ctx):
+    """Every word of every item: which child is popped first, each box's pass, each entry distance t0 (as bits; two NaNs
+    compare equal) and the root cull against rec.t -- on random boxes, invDirection components of +-inf with the origin on
+    and off the slab planes, equal boxes, boxes behind the ray, rec.t equal to a t0, rec.t = kInfinity and NaN box words
+    (arith_ref.child_pair_set)."""
+    x = R.child_pair_set()
+    want = R.child_pair_model(x)
+    exact, fast = _run(gpu_ctx, 8, EXACT, x), _run(gpu_ctx, 8, FAST, x)
+    _same_bits(exact, want, "child_pair / root_survives against the oracle's expressions")
+    _same_bits(fast, exact, "the fast mode's words against the exact mode's")

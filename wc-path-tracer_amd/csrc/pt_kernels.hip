@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_mk_tail(const wcpt_scene
 }
 
 /* Derived triangle records (pt_device.h), single and pair formats: one thread per pair. Same subtractions as
- * rayTriangle (:122-123). The second slot of the last pair of an odd count is NaN (never inside a leaf's range:
+ * rayTriangleE's edges (:122-123). The second slot of the last pair of an odd count is NaN (never inside a leaf's range:
  * leaf_record bounds leaves by the triangle count). A vertex index past the vertex buffer gives NaN vertices. */
 __device__ __forceinline__ void tri_fields(const uint32_t* __restrict__ idx, const float* __restrict__ vtx, uint32_t nvert,
                                            uint64_t k, float f[9])

@@ -164,7 +164,8 @@ __global__ __launch_bounds__(256) void pt_selftest_geometry(const uint32_t* __re
     auto v3 = [&](uint32_t k) { return mk3(f(k), f(k + 1u), f(k + 2u)); };
     auto put = [&](uint32_t k, float v) { y[k] = __float_as_uint(v); };
     auto put3 = [&](uint32_t k, f3 v) { put(k, v.x); put(k + 1u, v.y); put(k + 2u, v.z); };
-    Ray r; /* fn 0..4 and 7 start with origin, direction (fn 5 and 6 have fewer words: nothing else is read for them) */
+    Ray r; /* fn 0..4 and 7 start with origin, direction (fn 5 and 6 have fewer words: nothing else is read for them;
+              fn 8 brings its own invDirection) */
     if constexpr (FN <= 4 || FN == 7) {
         r.origin = v3(0);
         r.direction = v3(3);
@@ -249,6 +250,25 @@ __global__ __launch_bounds__(256) void pt_selftest_geometry(const uint32_t* __re
         put3(3, ps.ray.direction);
         put3(6, ps.transmittance);
         y[9] = rng;
+    } else if constexpr (FN == 8) { /* origin, invDirection, the left and the right child's box (min, max), rec.t: the
+                                       child-pair decision, and the root cull of the left box (no fast form: A is unused) */
+        r.origin = v3(0);
+        r.direction = mk3(0.0f, 0.0f, 0.0f); /* the box test reads invDirection alone */
+        r.invDirection = v3(3);
+        auto box = [&](uint32_t k) {
+            NodeV n; /* {min.xyz, max.x | max.yz, left, count} */
+            n.a = v4f{f(k), f(k + 1u), f(k + 2u), f(k + 3u)};
+            n.b = v4u{x[k + 4u], x[k + 5u], 0u, 0u};
+            return n;
+        };
+        const NodeV L = box(6), R = box(12);
+        const ChildPair c = child_pair(r, L, R);
+        y[0] = c.leftFirst ? 1u : 0u;
+        y[1] = c.passL ? 1u : 0u;
+        y[2] = c.passR ? 1u : 0u;
+        put(3, c.l0);
+        put(4, c.r0);
+        y[5] = root_survives(r, L, f(18)) ? 1u : 0u;
     }
 }
 
@@ -263,8 +283,8 @@ hipError_t launch_selftest(int fn, const uint32_t* in, const uint32_t* in2, uint
 
 bool selftest_geometry_words(int fn, uint32_t& in_words, uint32_t& out_words)
 {
-    static const uint32_t words[8][2] = {{15, 1}, {24, 4}, {24, 4}, {10, 1}, {11, 7}, {8, 7}, {3, 6}, {33, 10}};
-    if (fn < 0 || fn > 7) return false;
+    static const uint32_t words[9][2] = {{15, 1}, {24, 4}, {24, 4}, {10, 1}, {11, 7}, {8, 7}, {3, 6}, {33, 10}, {19, 6}};
+    if (fn < 0 || fn > 8) return false;
     in_words = words[fn][0];
     out_words = words[fn][1];
     return true;
@@ -293,6 +313,7 @@ hipError_t launch_selftest_geometry(int fn, int arith, const uint32_t* in, uint3
         WCPT_GEOMETRY_CASE(5)
         WCPT_GEOMETRY_CASE(6)
         WCPT_GEOMETRY_CASE(7)
+        WCPT_GEOMETRY_CASE(8)
     default: return hipErrorInvalidValue;
     }
 #undef WCPT_GEOMETRY_CASE

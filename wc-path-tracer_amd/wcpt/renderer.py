@@ -222,7 +222,8 @@ class Context:
         self._chk(lib.wcpt_selftest_device(self.h, fn, ptr(x), x2p, ptr(out), x.size))
         return out
 
-    GEOMETRY_WORDS = {0: (15, 1), 1: (24, 4), 2: (24, 4), 3: (10, 1), 4: (11, 7), 5: (8, 7), 6: (3, 6), 7: (33, 10)}
+    GEOMETRY_WORDS = {0: (15, 1), 1: (24, 4), 2: (24, 4), 3: (10, 1), 4: (11, 7), 5: (8, 7), 6: (3, 6), 7: (33, 10),
+                      8: (19, 6)}
 
     def selftest_geometry(self, fn: int, arith: int, x: np.ndarray, out_words: int | None = None) -> np.ndarray:
         """wcpt_selftest_geometry on the items x[n, in_words] (32-bit words): the output words, [n, out_words]."""
