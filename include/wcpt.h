@@ -619,6 +619,24 @@ int      wcpt_runtime_version(int* version);
 int      wcpt_profile_begin(wcpt_context* ctx);
 int      wcpt_profile_end(wcpt_context* ctx, double* kernel_ms_total, uint32_t* launches);
 
+/* ---- BVH build on the device ------------------------------------------------------------------------ */
+/* The midpoint BVH of the triangles indices[0 .. index_count) over `vertices` (float[3] at stride 12), built on the
+ * context's device from three context buffers; nothing leaves the device. Permutes `indices` in place and writes
+ * nodes[0 .. *nodes_used): afterwards both hold exactly the bytes wcpt_bvh_build (below) produces from the same positions
+ * and the same starting index order -- bounds, counts, leftNodeOrTriangleIndex, node numbering, permutation. The contents
+ * of `nodes` past *nodes_used are unspecified. Synchronous: runs on the context's stream, behind the frame-overlap
+ * pipes, and returns when its work has finished.
+ * WCPT_ERROR_INVALID_ARGUMENT, with neither buffer written: an unknown handle (or one buffer passed twice);
+ * index_count zero or no multiple of 3; vertex_count * 12 or index_count * 4 beyond its buffer; `nodes` smaller than
+ * 2 * index_count / 3 nodes; an index >= vertex_count (found on the device by a pass that reads only the indices, before
+ * any vertex is read); a referenced coordinate that is not finite -- a difference from wcpt_bvh_build, which folds NaNs
+ * in index order: min as a < b ? a : b is not associative once a NaN is present, so no parallel reduction has its bits.
+ * For the runtime's caches the call is a write of `indices` and `nodes`, exactly as wcpt_buffer_upload of both: a render
+ * that follows needs no option change. Scratch memory (about 300 bytes per triangle) belongs to the context: allocated
+ * by the first call, grown on demand, freed by wcpt_destroy. */
+int      wcpt_bvh_build_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t vertex_count, wcpt_buffer indices,
+                               uint32_t index_count, wcpt_buffer nodes, uint32_t* nodes_used);
+
 /* ---- host utilities (no GPU needed) ----------------------------------------------------------------- */
 /* OBJ text -> unique (v,vt,vn) vertices + fan-triangulated indices (ModelLoader.jai:60-141). */
 int      wcpt_obj_parse(const char* text, uint64_t length, wcpt_mesh* out);

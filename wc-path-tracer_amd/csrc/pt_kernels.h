@@ -220,6 +220,14 @@ uint64_t bloom_pyramid_texels(uint32_t levels, const uint32_t* lw, const uint32_
 hipError_t launch_composite_bloom(const float4* img, uint32_t width, uint32_t height, float threshold, float knee,
                                   uint32_t levels, const uint32_t* lw, const uint32_t* lh, float4* down, float4* up, void* dst,
                                   bool rgba8, hipStream_t stream);
+/* wcpt_bvh_build_device (pt_bvh_build.hip; the rule in bvh_midpoint.h): the midpoint BVH of the triangles
+ * indices[0 .. index_count) over `vertices` into `nodes` (2 * index_count / 3 of them) with `indices` permuted, in
+ * `scratch` of bvh_build_scratch_bytes(index_count) bytes. Blocks the host: *status is 0 and *nodes_used the node count
+ * when the tree was built; else *status holds bvh_midpoint.h kBvhBadIndex / kBvhNotFinite and nothing was written to
+ * `indices` or `nodes`. No vertex is read unless every index is below vertex_count. */
+uint64_t bvh_build_scratch_bytes(uint32_t index_count);
+hipError_t bvh_build_device(const float* vertices, uint32_t vertex_count, uint32_t* indices, uint32_t index_count,
+                            void* nodes, void* scratch, uint32_t* status, uint32_t* nodes_used, hipStream_t stream);
 /* overlap: WCPT_OPTION_FRAME_OVERLAP as the runtime allows it for this render (0 off, 1 auto, 2 on whenever the tiles
  * are cost-ordered); with 0 a pending overlap is joined first and the frame runs on `stream` */
 hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkState& mk, hipStream_t stream,

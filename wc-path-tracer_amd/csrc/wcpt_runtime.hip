@@ -20,6 +20,7 @@
 #include "../../include/wcpt.h"
 #include "pt_kernels.h"
 #include "wcpt_bloom.h"
+#include "bvh_midpoint.h"
 
 namespace {
 
@@ -58,6 +59,12 @@ void shadow_mark(Buffer& b, uint64_t offset, uint64_t end)
     if (b.known.empty()) return;
     const uint64_t c0 = (offset + kShadowChunk - 1) / kShadowChunk, c1 = end / kShadowChunk;
     for (uint64_t c = c0; c < c1 && c < b.known.size(); c++) b.known[c] = 1;
+}
+
+/* The chunks that [offset, end) touches no longer hold what the device holds (a kernel wrote the range). */
+void shadow_forget(Buffer& b, uint64_t offset, uint64_t end)
+{
+    for (uint64_t c = offset / kShadowChunk; c < (end + kShadowChunk - 1) / kShadowChunk && c < b.known.size(); c++) b.known[c] = 0;
 }
 
 /* True when the host copy holds every byte of [offset, offset + bytes). */
@@ -142,6 +149,8 @@ struct wcpt_context {
     uint32_t* d_scan = nullptr;        /* leaf-count scan flag (prepare_tri_records) */
     float4* d_bloom = nullptr;         /* wcpt_composite_bloom: the down pyramid, then the up pyramid (on first use) */
     uint64_t bloom_bytes = 0;
+    void* d_bvh = nullptr;             /* wcpt_bvh_build_device: its scratch (on first use, grown on demand) */
+    uint64_t bvh_bytes = 0;
     uint64_t scratch_bytes = 0;
     int kernel = WCPT_KERNEL_MEGAKERNEL;
     int kernel_run = WCPT_KERNEL_MEGAKERNEL; /* the variant the current/last render runs (WCPT_KERNEL_AUTO resolved) */
@@ -987,6 +996,7 @@ int wcpt_destroy(wcpt_context* ctx)
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_scan) (void)hipFree(ctx->d_scan);
     if (ctx->d_bloom) (void)hipFree(ctx->d_bloom);
+    if (ctx->d_bvh) (void)hipFree(ctx->d_bvh);
     for (auto& p : ctx->events) {
         (void)hipEventDestroy(p.first);
         (void)hipEventDestroy(p.second);
@@ -1238,6 +1248,52 @@ int wcpt_buffer_free(wcpt_context* ctx, wcpt_buffer buf)
     if (it->second.raw) HIP_TRY(ctx, hipFree(it->second.raw), "hipFree");
     ctx->buffers.erase(it);
     ctx->generation++;
+    return WCPT_SUCCESS;
+}
+
+/* ---- BVH build on the device (pt_bvh_build.hip) --------------------------------------------------- */
+int wcpt_bvh_build_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t vertex_count, wcpt_buffer indices,
+                          uint32_t index_count, wcpt_buffer nodes, uint32_t* nodes_used)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    Buffer* bv = find_buffer(ctx, vertices);
+    Buffer* bi = find_buffer(ctx, indices);
+    Buffer* bn = find_buffer(ctx, nodes);
+    if (!bv || !bi || !bn) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: unknown buffer handle");
+    if (bv == bi || bv == bn || bi == bn) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: the three buffers must differ");
+    if (!nodes_used) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: null nodes_used");
+    if (index_count == 0 || index_count % 3 != 0)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: index_count %u is zero or no multiple of 3", index_count);
+    if ((uint64_t)vertex_count * 12ull > bv->bytes)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: %u vertices exceed the vertex buffer (%llu bytes)",
+                         vertex_count, (unsigned long long)bv->bytes);
+    if ((uint64_t)index_count * 4ull > bi->bytes)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: %u indices exceed the index buffer (%llu bytes)",
+                         index_count, (unsigned long long)bi->bytes);
+    const uint64_t node_bound = 2ull * index_count / 3ull;
+    if (bn->bytes / sizeof(wcpt_node) < node_bound)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: the node buffer holds %llu nodes, %llu needed",
+                         (unsigned long long)(bn->bytes / sizeof(wcpt_node)), (unsigned long long)node_bound);
+    const uint64_t need = wcpt::bvh_build_scratch_bytes(index_count);
+    if (ctx->bvh_bytes < need) {
+        rc = grow(ctx, ctx->d_bvh, ctx->bvh_bytes, need, need, "hipMalloc(bvh build scratch)");
+        if (rc) return rc;
+    }
+    uint32_t status = 0, used = 0;
+    HIP_TRY(ctx, wcpt::bvh_build_device(static_cast<const float*>(bv->ptr), vertex_count, static_cast<uint32_t*>(bi->ptr),
+                                        index_count, bn->ptr, ctx->d_bvh, &status, &used, ctx->stream), "bvh build");
+    if (status & wcpt::kBvhBadIndex)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: an index is not below vertex_count %u", vertex_count);
+    if (status & wcpt::kBvhNotFinite)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: a referenced coordinate is not finite");
+    /* a write of both buffers, as wcpt_buffer_upload's: the host copies no longer know the range, and everything keyed
+     * on the generations (triangle records, leaf scan, tiny-tree flag, frame preparation, primary cache) is re-learned */
+    shadow_forget(*bi, 0, (uint64_t)index_count * 4ull);
+    shadow_forget(*bn, 0, (uint64_t)used * sizeof(wcpt_node));
+    bi->generation = ++ctx->generation;
+    bn->generation = ++ctx->generation;
+    *nodes_used = used;
     return WCPT_SUCCESS;
 }
 

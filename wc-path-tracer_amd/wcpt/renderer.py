@@ -113,6 +113,14 @@ class Context:
             self.buffer_upload(b, a)
         return b
 
+    def bvh_build_device(self, vb: int, vertex_count: int, ib: int, index_count: int, nb: int) -> int:
+        """wcpt_bvh_build_device: the midpoint BVH of the index buffer `ib` over the vertex buffer `vb`, built on the
+        device into the node buffer `nb` (at least 2 * index_count / 3 nodes), `ib` permuted in place -- the bytes of
+        wcpt_bvh_build. Returns the node count."""
+        used = C.c_uint32()
+        self._chk(lib.wcpt_bvh_build_device(self.h, vb, vertex_count, ib, index_count, nb, C.byref(used)))
+        return used.value
+
     # -- image ----------------------------------------------------------------------------------------
     def create_screen(self, width: int, height: int):
         self._chk(lib.wcpt_create_screen(self.h, width, height))
@@ -378,6 +386,7 @@ class PathTracingRenderer:
         self.materials = np.zeros(0, dtype=MATERIAL_DTYPE)
         self.spheres = np.zeros(0, dtype=SPHERE_DTYPE)
         self.meshes = []
+        self.build = "host"              # Init's `build`: where LoadModel builds each mesh's BVH
         self.ctx = Context(device)
         if arith != ARITH_EXACT:
             self.ctx.set_option(OPTION_ARITH, arith)
@@ -385,11 +394,18 @@ class PathTracingRenderer:
         self._mesh_bufs = []
 
     # Init :272-343 — LoadModel + materials/spheres + UpdateMaterials
-    def Init(self, model_path: str | None = None, scene: "_scene.HostScene | None" = None):
+    def Init(self, model_path: str | None = None, scene: "_scene.HostScene | None" = None, build: str = "host"):
+        """build: "host" (default) uploads trees built by wcpt_bvh_build; "device" uploads each mesh's positions and
+        indices as they are and builds the same tree there (wcpt_bvh_build_device), so a model is loaded without the
+        host builder's stall."""
+        if build not in ("host", "device"):
+            raise ValueError(f"unknown build {build!r}")
+        self.build = build
         if scene is None:
             scene = _scene.generate("default")
             if model_path is not None:
-                scene.meshes = [_scene.bvh_build(_scene.obj_load(model_path))]
+                mesh = _scene.obj_load(model_path)
+                scene.meshes = [mesh if build == "device" else _scene.bvh_build(mesh)]
         self.materials = scene.materials.copy()
         self.spheres = scene.spheres.copy()
         self.meshes = list(scene.meshes)
@@ -400,8 +416,11 @@ class PathTracingRenderer:
     def LoadModel(self):
         draws = np.zeros(len(self.meshes), dtype=DRAW_COMMAND_DTYPE)
         for i, m in enumerate(self.meshes):
-            vb, ib, nb = (self.ctx.buffer_from(m.positions), self.ctx.buffer_from(m.indices),
-                          self.ctx.buffer_from(m.nodes))
+            if self.build == "device":
+                vb, ib, nb, _ = _scene.device_bvh_build(self.ctx, _scene.HostMesh(m.positions, m.indices))
+            else:
+                vb, ib, nb = (self.ctx.buffer_from(m.positions), self.ctx.buffer_from(m.indices),
+                              self.ctx.buffer_from(m.nodes))
             self._mesh_bufs += [vb, ib, nb]
             draws[i] = (self.ctx.buffer_address(vb), self.ctx.buffer_address(ib), self.ctx.buffer_address(nb),
                         m.indices.size, 0)
