@@ -1,4 +1,4 @@
-"""Frame preparation on the GPU (wcpt_runtime.hip prepare_tri_records, csrc/frame_prep.h): one context renders a sequence
+"""Frame preparation on the GPU (wcpt_render.hip prepare_tri_records, csrc/frame_prep.h): one context renders a sequence
 of frames that takes each preparation path in turn -- a miss, an unchanged frame, a moved camera, an option change that
 reuses the records, a re-uploaded mesh that rebuilds them, the triangle cache off and on again -- and every frame equals,
 bit for bit, the same frame rendered by a context created fresh for it, which can only take the miss path. The fresh

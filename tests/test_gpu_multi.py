@@ -713,6 +713,52 @@ def test_context_row_stripes_and_frame_row_output(gpu_ctx, kernel):
         assert (wire[other] == -7.0).all()
 
 
+@pytest.mark.parametrize("kernel", [wcpt.KERNEL_MEGAKERNEL, wcpt.KERNEL_WAVEFRONT])
+def test_context_screen_transitions(gpu_ctx, kernel):
+    """What a resize, a row range and row stripes do to the rows one context holds (csrc/screen_layout.h, on the device):
+    after every step wcpt_readback accepts exactly width * rows * 16 bytes, and a render fills those rows with the rows
+    of a whole-frame render of the same size, bit for bit (seeds are global)."""
+    s = get_scene("cornell")
+    W = 16
+    ref = {H: _context_frames(s, W, H, (0,), kernel=kernel) for H in (12, 9, 8)}
+
+    def holds(ctx, dev, H, want):
+        """the context holds the frame rows `want` of the W x H frame"""
+        ctx.render(s.scene_data(W, H, max_bounce=4, frame=0), *dev.addresses())
+        ctx.sync()
+        blk = ctx.readback(len(want))
+        with pytest.raises(wcpt.WcptError):
+            ctx.readback(len(want) + 1)
+        assert np.array_equal(blk.view(np.uint32), ref[H][want].view(np.uint32)), (H, want)
+
+    with wcpt.Context(0) as ctx:
+        dev = wcpt.DeviceScene(ctx, s)
+        ctx.set_kernel(kernel)
+        ctx.create_screen(W, 12)
+        holds(ctx, dev, 12, list(range(12)))
+        ctx.set_row_range(4, 6)                  # 1: a block of rows 4..9 ...
+        holds(ctx, dev, 12, list(range(4, 10)))
+        ctx.resize(W, 8)                         # ... clipped to rows 4..7 by a frame of 8 rows
+        holds(ctx, dev, 8, list(range(4, 8)))
+        ctx.resize(W, 12)                        # (the block stays clipped)
+        holds(ctx, dev, 12, list(range(4, 8)))
+        ctx.set_row_stripes(0, 6, 2, 4)          # 2: stripes of 2 rows every 4 rows: rows 0,1, 4,5, 8,9 ...
+        holds(ctx, dev, 12, [0, 1, 4, 5, 8, 9])
+        ctx.resize(W, 9)                         # ... whose last row a frame of 9 rows cuts off: the whole frame again
+        holds(ctx, dev, 9, list(range(9)))
+        dev.free()
+    with wcpt.Context(0) as ctx:
+        dev = wcpt.DeviceScene(ctx, s)
+        ctx.set_kernel(kernel)
+        ctx.set_row_range(7, 3)                  # 3: a range before the first screen is honoured by it
+        ctx.create_screen(W, 12)
+        holds(ctx, dev, 12, [7, 8, 9])
+        ctx.set_row_range(0, 0)                  # 4: rows = 0 restores the whole frame
+        holds(ctx, dev, 12, list(range(12)))
+        dev.free()
+    del s
+
+
 def test_row_stripe_errors(gpu_ctx):
     s = get_scene("cornell")
     with wcpt.Context(0) as ctx:

@@ -48,6 +48,7 @@
 #include "group_plan.h"
 #include "group_wait.h"
 #include "pt_kernels.h"
+#include "screen_layout.h"
 
 static_assert(sizeof(ncclUniqueId) == WCPT_GROUP_UNIQUE_ID_BYTES, "WCPT_GROUP_UNIQUE_ID_BYTES");
 
@@ -915,24 +916,15 @@ wcpt_context* wcpt_group_context(wcpt_group* g, int rank)
 int wcpt_row_block(uint32_t height, uint32_t n, uint32_t rank, uint32_t* y0, uint32_t* rows)
 {
     if (!y0 || !rows || n == 0 || rank >= n) return WCPT_ERROR_INVALID_ARGUMENT;
-    const uint32_t a = (uint32_t)((uint64_t)rank * height / n);
-    const uint32_t b = (uint32_t)((uint64_t)(rank + 1) * height / n);
-    *y0 = a;
-    *rows = b - a;
+    wcpt::split_row_block(height, n, rank, *y0, *rows);
     return WCPT_SUCCESS;
 }
 
 int wcpt_row_stripes(uint32_t height, uint32_t n, uint32_t rank, uint32_t stripe, uint32_t* y_first, uint32_t* rows)
 {
     if (stripe == 0) return wcpt_row_block(height, n, rank, y_first, rows);
-    if (!y_first || !rows || n == 0 || rank >= n || (stripe & (stripe - 1u))) return WCPT_ERROR_INVALID_ARGUMENT;
-    /* stripes s = rank, rank + n, ... below T = ceil(height / stripe); only the frame's last stripe can be short */
-    const uint64_t T = ((uint64_t)height + stripe - 1u) / stripe;
-    const uint64_t count = T > rank ? (T - 1u - rank) / n + 1u : 0u;
-    uint64_t r = count * stripe;
-    if (count && (T - 1u - rank) % n == 0 && height % stripe) r -= stripe - height % stripe; /* it holds the short one */
-    *y_first = rank * stripe;
-    *rows = (uint32_t)r;
+    if (!y_first || !rows || n == 0 || rank >= n || !wcpt::stripe_pow2(stripe)) return WCPT_ERROR_INVALID_ARGUMENT;
+    wcpt::split_row_stripes(height, n, rank, stripe, *y_first, *rows);
     return WCPT_SUCCESS;
 }
 
@@ -940,7 +932,7 @@ int wcpt_group_set_option(wcpt_group* g, int option, int value)
 {
     if (!g) return group_error(WCPT_ERROR_INVALID_HANDLE, "null group");
     if (option == WCPT_GROUP_OPTION_ROW_STRIPE) {
-        if (value < 0 || value > 32768 || (value & (value - 1)))
+        if (value < 0 || (value && !wcpt::stripes_ok((uint32_t)value, (uint32_t)value)))
             return group_error(WCPT_ERROR_INVALID_ARGUMENT, "row stripe %d (0, or a power of two up to 32768)", value);
         if (g->broken) return group_error(WCPT_ERROR_DEVICE_LOST, "group aborted after a transport failure");
         const int rc = wcpt_group_sync(g); /* queued frames keep the split they were issued with */

@@ -49,7 +49,7 @@ OPTION_TRIANGLE_CACHE = 5
 OPTION_PAIR_RECORDS = 6
 OPTION_PACKED_REFS = 7
 OPTION_WF_REFILL = 8
-DEFAULT_WF_REFILL = 20  # wcpt_runtime.hip
+DEFAULT_WF_REFILL = 20  # wcpt_context.h
 OPTION_MK_TILE_ORDER = 9
 OPTION_WF_PIPES = 10
 OPTION_PROFILE_REGION = 11
@@ -63,7 +63,7 @@ OPTION_MK_SPLIT = 18    # split renders: -1 automatic, 0 never, k = cut before s
 OPTION_MK_TINY_TREE = 19  # tiny trees walked without the traversal loop: -1 automatic, 0 never, 1 on (csrc/mk_tiny_rule.h)
 ARITH_EXACT = 0
 ARITH_FAST = 1
-DEFAULT_WF_PIPES = 0  # wcpt_runtime.hip: by queue length (2 or 3)
+DEFAULT_WF_PIPES = 0  # wcpt_context.h: by queue length (2 or 3)
 
 # gather payload formats (wcpt_set_gather_output, wcpt_group_set_output)
 PAYLOAD_RGB32F = 3
