@@ -53,7 +53,11 @@ extern "C" {
 #define WCPT_ERROR_UNKNOWN               (-13)
 #define WCPT_ERROR_INVALID_ARGUMENT      (-1000)
 #define WCPT_ERROR_INVALID_HANDLE        (-1001)
-#define WCPT_ERROR_STACK_OVERFLOW        (-1002) /* BVH deeper than the traversal stack */
+/* A far child did not fit the 48-entry traversal stack: the push is refused, nothing is written past
+ * the stack, and that subtree is not visited. wcpt_render itself returns success; the next wcpt_sync or wcpt_readback
+ * reports the error once and clears it. wcpt_render_counters on such a tree returns it too, and the counters it wrote
+ * are those of the cut-short traversal, not the reference's. */
+#define WCPT_ERROR_STACK_OVERFLOW        (-1002)
 #define WCPT_ERROR_NO_SCREEN             (-1003) /* wcpt_render before wcpt_create_screen */
 #define WCPT_ERROR_PARSE                 (-1004) /* OBJ text could not be parsed */
 
@@ -395,7 +399,8 @@ int      wcpt_set_row_stripes(wcpt_context* ctx, uint32_t y_first, uint32_t rows
 uint64_t wcpt_image_device_ptr(wcpt_context* ctx);                 /* float4[rows][width], pitch width*16 */
 /* Render into caller-owned device memory (e.g. a torch tensor handed to RCCL, or imported interop memory)
  * instead of the context's own image. `bytes` must hold width*rows*16. device_ptr == 0 reverts to the
- * context-owned image. The caller keeps ownership. */
+ * context-owned image. The caller keeps ownership. device_ptr must be 16-byte aligned (the kernels store float4
+ * texels); one that is not is WCPT_ERROR_INVALID_ARGUMENT and the image in use stays. */
 int      wcpt_set_external_image(wcpt_context* ctx, uint64_t device_ptr, uint64_t bytes);
 /* Gather payload written by the render itself: every wcpt_render also stores each pixel it
  * finishes into caller-owned device memory at `device_ptr`, row-major [rows][width], in payload format `channels`:

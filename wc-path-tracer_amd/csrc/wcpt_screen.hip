@@ -52,10 +52,16 @@ int apply_layout(wcpt_context* ctx, const wcpt::ScreenLayout& next, bool zero)
 }
 
 /* wcpt_set_row_range and wcpt_set_row_stripes name the context's rows: they are its rows from the call on, also when
- * the image then cannot be brought to hold them and the call fails. */
+ * the image then cannot be brought to hold them and the call fails. An external image is the exception: the context
+ * cannot grow it, and a render of rows it does not hold would write past the caller's memory, so rows it cannot hold
+ * are refused before anything changes. */
 int apply_named_rows(wcpt_context* ctx, const wcpt::ScreenLayout& next)
 {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    if (ctx->external_bytes && next.height) {
+        const int rc = alloc_image(ctx, layout_bytes(next));
+        if (rc) return rc;
+    }
     ctx->layout.y0 = next.y0;
     ctx->layout.rows = next.rows;
     return apply_layout(ctx, next, false);
@@ -146,6 +152,7 @@ int wcpt_set_external_image(wcpt_context* ctx, uint64_t device_ptr, uint64_t byt
         return WCPT_SUCCESS;
     }
     if (bytes == 0) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "external image of 0 bytes");
+    if (device_ptr & 15u) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "external image needs 16-byte alignment");
     if (ctx->layout.width && layout_bytes(ctx->layout) > bytes)
         return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "external image too small for %ux%u", ctx->layout.width,
                          ctx->layout.rows);
