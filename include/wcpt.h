@@ -382,7 +382,16 @@ uint64_t wcpt_buffer_device_address(wcpt_context* ctx, wcpt_buffer buf); /* 0 on
 int      wcpt_buffer_free(wcpt_context* ctx, wcpt_buffer buf);
 
 /* ---- output image (CreateScreen / Resize) --------------------------------------------------------- */
-/* The context-owned image starts as zeros (the reference's is undefined; its editor blends frame 1 with it). */
+/* Frame sizes. The frame may be any width x height >= 1 of 32 bits, also one of 2^32 pixels or more: a pixel's seed is
+ * pcg_hash(x + y * width + renderedFramesCount * 719393) in 32-bit arithmetic, wrapping as the reference's uint does
+ * (pathTracer.comp:304), for every renderedFramesCount up to 0xFFFFFFFF (where the reference's 1 / float(count + 1) is a
+ * division by zero and the accumulated RGB is NaN, here too). What is limited is what one context holds: its rows
+ * (the whole frame, or the rows named by wcpt_set_row_range / wcpt_set_row_stripes) are rendered in 8x8 tiles of 64
+ * lanes and may cover at most 2^32 - 64 lanes, ceil(width / 8) * ceil(rows / 8) * 64 -- an image of just under 64 GiB.
+ * wcpt_render and wcpt_render_counters of more are WCPT_ERROR_INVALID_ARGUMENT, with a message, before anything is
+ * launched; the context stays usable (name fewer rows). A larger frame is rendered in row blocks or stripes: rows named
+ * before the first wcpt_create_screen are honoured by it, so only they are allocated.
+ * The context-owned image starts as zeros (the reference's is undefined; its editor blends frame 1 with it). */
 int      wcpt_create_screen(wcpt_context* ctx, uint32_t width, uint32_t height);
 int      wcpt_resize(wcpt_context* ctx, uint32_t width, uint32_t height);
 /* Row-block shard: this context renders and stores only rows [y0, y0+rows) of the width x height

@@ -78,4 +78,8 @@ extern "C" void sl_split(uint32_t height, uint32_t n, uint32_t rank, uint32_t st
     else split_row_block(height, n, rank, out[0], out[1]);
 }
 
+// the 8x8 tiles of the layout's rows, and whether a render can address them
+extern "C" uint64_t sl_tiles(const uint32_t* l) { return layout_tiles(unpack(l)); }
+extern "C" int sl_renderable(const uint32_t* l) { return layout_renderable(unpack(l)) ? 1 : 0; }
+
 extern "C" int sl_stripe_pow2(uint32_t stripe) { return stripe_pow2(stripe) ? 1 : 0; }

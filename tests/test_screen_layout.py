@@ -39,6 +39,9 @@ def sl(tmp_path_factory):
     lib.sl_frame_row.restype = u32
     lib.sl_split.argtypes = [u32, u32, u32, u32, p]
     lib.sl_stripe_pow2.argtypes = [u32]
+    lib.sl_tiles.argtypes = [p]
+    lib.sl_tiles.restype = ctypes.c_uint64
+    lib.sl_renderable.argtypes = [p]
     return lib
 
 
@@ -72,6 +75,30 @@ def test_row_map_of_a_layout(sl):
     assert _rows(sl, (16, 10, 0, 6, 4, 8, 1)) == [0, 1, 2, 3, 8, 9]        # a short last stripe
     assert sl.sl_last_row(_words((16, 20, 0, 10, 2, 4, 1))) == 17
     assert sl.sl_last_row(_words((0, 0, 0xFFFFFFF0, 32, 1, 1, 1))) == 0xFFFFFFF0 + 31   # 64 bits: no wrap
+
+
+def test_rows_a_render_can_address(sl):
+    """include/wcpt.h, "Frame sizes": a context's rows may cover at most 2^26 - 1 tiles of 8x8 pixels (2^32 - 64 lanes),
+    whatever the size of the frame around them; counted in 64 bits, so no product wraps into the accepted range."""
+    def tiles(layout):
+        return int(sl.sl_tiles(_words(layout)))
+
+    def ok(layout):
+        return sl.sl_renderable(_words(layout)) == 1
+    assert tiles(whole(1, 1)) == 1 and tiles(whole(9, 9)) == 4 and tiles(whole(70, 1)) == 9 and ok(whole(1, 1))
+    band = (65521, 65599, 65548, 8, 0, 0, 1)                  # 8 rows of a frame of more than 2^32 pixels
+    assert tiles(band) == 8191 and ok(band)
+    assert tiles(whole(65521, 65599)) == 8191 * 8200 and not ok(whole(65521, 65599))
+    # the boundary: 2^26 - 1 tiles fit, 2^26 do not
+    for layout in (whole(65536, 65528), whole(65528, 65536)):
+        assert tiles(layout) == 2 ** 26 - 8192 and ok(layout)
+    row = ((2 ** 26 - 1) * 8, 8, 0, 8, 0, 0, 0)
+    assert tiles(row) == 2 ** 26 - 1 and ok(row)
+    assert tiles(whole(65536, 65536)) == 2 ** 26 and not ok(whole(65536, 65536))
+    assert tiles(whole(65529, 65536)) == 2 ** 26 and not ok(whole(65529, 65536))      # partial tiles count whole
+    big = (0xFFFFFFFF, 0xFFFFFFFF, 0, 0xFFFFFFFF, 0, 0, 0)
+    assert tiles(big) == 2 ** 58 and not ok(big)                                       # no wrap in 64 bits
+    assert not ok((0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFF0, 8, 0, 0, 1))                    # 2^29 tiles in one tile row
 
 
 def test_set_row_stripes(sl):

@@ -52,6 +52,18 @@ inline RowMap layout_row_map(const ScreenLayout& l)
 /* The frame row of the layout's last local row (its rows must be > 0), in 64 bits. */
 inline uint64_t layout_last_row(const ScreenLayout& l) { return frame_row64(layout_row_map(l), l.rows - 1u); }
 
+/* What a render can address (include/wcpt.h, "Frame sizes"). The frame may be any width x height of 32 bits: a pixel's
+ * seed takes x + y * width in 32-bit arithmetic, wrapping as the reference's uint does. The context's own rows are
+ * rendered in 8x8 tiles of 64 lanes, and tiles, lanes, path slots and queue entries are counted in 32 bits: its rows
+ * may cover at most kMaxTiles tiles, 2^32 - 64 lanes (the wavefront's grid-stride loops add up to 64 to an index before
+ * they compare it), that is an image of just under 64 GiB. At most 2^29 x 2^29 tiles: the product fits 64 bits. */
+constexpr uint64_t kMaxTiles = 0x3FFFFFFull;
+inline uint64_t layout_tiles(const ScreenLayout& l)
+{
+    return (((uint64_t)l.width + 7u) / 8u) * (((uint64_t)l.rows + 7u) / 8u);
+}
+inline bool layout_renderable(const ScreenLayout& l) { return layout_tiles(l) <= kMaxTiles; }
+
 /* `old` holding `rows` rows from frame row y0, in stripes or (stripe 0) as one block */
 inline ScreenLayout layout_with_rows(ScreenLayout old, uint32_t y0, uint32_t rows, uint32_t stripe, uint32_t period)
 {

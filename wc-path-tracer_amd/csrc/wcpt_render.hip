@@ -305,6 +305,11 @@ int check_render_args(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t 
     if (!scene) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "wcpt_render: null SceneData");
     if (!ctx->image || ctx->layout.width == 0 || ctx->layout.rows == 0)
         return set_error(ctx, WCPT_ERROR_NO_SCREEN, "wcpt_render: no output image (call wcpt_create_screen)");
+    if (!wcpt::layout_renderable(ctx->layout))
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT,
+                         "wcpt_render: the context's %u rows of width %u cover %llu 8x8 tiles, more than 2^26 - 1 "
+                         "(name fewer rows with wcpt_set_row_range or wcpt_set_row_stripes)", ctx->layout.rows,
+                         ctx->layout.width, (unsigned long long)wcpt::layout_tiles(ctx->layout));
     if (scene->sphereCount > 0 && spheres == 0)
         return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "wcpt_render: sphereCount > 0 with a null sphere buffer");
     if (scene->drawCommandCount > 0 && draws == 0)
