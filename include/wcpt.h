@@ -151,10 +151,12 @@ extern "C" {
 #define WCPT_OPTION_FRAME_OVERLAP 15
 /* Primary cache (megakernel). The primary ray of a pixel depends only on the pixel, the frame size, inverseProjection,
  * inverseView and position -- no random number -- so while the camera and the scene stand still every progressive frame
- * finds the primary Intersect record (t, primitive, draw) of the frame before. 1 (default): the first render after
- * frame 0 of such a sequence stores each pixel's record (8 bytes per pixel with one draw command, 12 with several) and
- * the renders that follow read it instead of tracing the primary segment; hit resolution and shading run as ever, from
- * the current buffers. A render with renderedFramesCount == 0 drops the cache and renders plainly, so a camera that
+ * finds the primary segment of the frame before. 1 (default): the first render after frame 0 of such a sequence stores
+ * each pixel's resolved primary segment -- the ray's direction, the hit's distance, facing, normal and material index:
+ * 32 bytes per pixel of the context's rows, whatever the number of draw commands (66 MB for 1920 x 1080), allocated
+ * when a render first writes -- and the renders that follow read it instead of computing the direction, tracing the
+ * primary segment and resolving its hit; shading runs as ever, from the current material buffer. A render with
+ * renderedFramesCount == 0 drops the cache and renders plainly, so a camera that
  * moves every frame pays nothing. The cache is also dropped when anything the record depends on changes: the camera's
  * bytes, sphereCount, drawCommandCount, the frame size or the context's rows, the sphere or draw-command address, any
  * wcpt_buffer_alloc / wcpt_buffer_upload / wcpt_buffer_free, an option change, or a render by the wavefront kernel.

@@ -6,7 +6,9 @@ Each variant is a comma list of option=value: stack=<0|1>, kernel=<0|2>, order=<
 BVH leaf order with identity indices: same triangles, same results, soup-like locality), arith=<0|1> (WCPT_OPTION_ARITH:
 1 = the megakernel's fast-arithmetic instances), mk_split=<-1|0|k> (WCPT_OPTION_MK_SPLIT: the megakernel cut before segment
 k into a head and a compacted tail launch; -1 = the automatic rule), tiny=<-1|0|1> (WCPT_OPTION_MK_TINY_TREE: a root leaf
-or a root over two leaves walked without the traversal loop). Prints the median ms/frame (HIP events on the context stream) and
+or a root over two leaves walked without the traversal loop), bounces=<n> (maxBounceCount of the variant's frames instead
+of the config's; 0 leaves segment 0 and the accumulation: the region the primary cache works on), pcache=<0|1>
+(WCPT_OPTION_PRIMARY_CACHE; with --frames above 2 a still-camera variant's frames are one plain, one write and reads). Prints the median ms/frame (HIP events on the context stream) and
 Mray/s. With --check, variants of the same arith are compared bit for bit; variants of different arith by the
 statistics of the fast mode's stated tolerance (wcpt.h WCPT_OPTION_ARITH): diverged pixels (some channel off by more than
 1e-5 * max(1, |ref|), or a finiteness mismatch), the median relative difference, mean |d| and the bit-equal share.
@@ -91,9 +93,13 @@ def main():
             ctx.set_option(wcpt._lib.OPTION_ARITH, int(o.get("arith", 0)))
             ctx.set_option(wcpt._lib.OPTION_MK_SPLIT, int(o.get("mk_split", -1)))
             ctx.set_option(wcpt._lib.OPTION_MK_TINY_TREE, int(o.get("tiny", -1)))
+            ctx.set_option(wcpt._lib.OPTION_PRIMARY_CACHE, int(o.get("pcache", 1)))
+            vsds = sds
+            if "bounces" in o:
+                vsds = [s.scene_data(W, H, max_bounce=int(o["bounces"]), samples=spp, frame=f) for f in range(a.frames)]
             dev = scenes[o.get("deindex", "0")]
             ctx.profile_begin()
-            for sd in sds:
+            for sd in vsds:
                 ctx.render(sd, *dev.addresses())
             ms, n = ctx.profile_end()
             ctx.sync()

@@ -101,7 +101,8 @@ struct MkSelection {
  *   - a split is taken only where a head exists (render, LDS stack, one sample: what mk_split_cut also demands);
  *   - the read form for one sample holds the sample count as a constant and is used only for samples == 1, every other
  *     sample count takes the reuse form; without a read, reuse is samples > 1;
- *   - a reuse-write build stores the record from the caller (shade_pixel), which the kernel derives from the pair. */
+ *   - a reuse-write build stores the cache entry from the caller (shade_pixel), after its sample loop, which the kernel
+ *     derives from the pair. */
 constexpr MkSelection mk_variant_select(int mode, int stack_kind, bool pair_records, uint32_t draws, uint32_t samples,
                                         int pcmode, int arith, bool split)
 {

@@ -1,13 +1,16 @@
 /* primary_cache_key.h — when the megakernel's primary cache (WCPT_OPTION_PRIMARY_CACHE) is valid. Host only, no HIP:
  * tests/primary_cache_key_shim.cpp compiles it with g++.
  *
- * A pixel's primary Intersect record (t, primitive, draw) is a function of its primary ray (the pixel, W, H,
- * inverseProjection, inverseView, position: pt_device.h primary_direction, no random number) and of the geometry the
- * ray meets (spheres, draw commands and what they point at). The key holds all of it that the runtime can see: the
+ * A cache entry is a pixel's resolved primary segment (primary_record.h: the primary ray's direction and resolve_hit's
+ * result for it -- distance, facing, normal, material index). It is a function of the primary ray (the pixel, W, H,
+ * inverseProjection, inverseView, position: pt_device.h primary_direction, no random number), of the geometry the
+ * ray meets (spheres, draw commands and what they point at; a sphere's material index comes from the sphere buffer) and
+ * of the arithmetic mode, which bumps the generation. A material's contents are not in it: they are read every frame.
+ * The key holds all of it that the runtime can see: the
  * camera's bytes, the two counts, the frame and the context's rows of it (they decide which pixel a record index is),
  * the addresses the kernel reads the geometry through, the leaf-record choice, and the context's generation counter,
  * which every buffer alloc / upload / free and every option change bumps. maxBounceCount, samples, the materials and
- * renderedFramesCount are not in it: the record does not depend on them. (renderedFramesCount == 0 drops the cache
+ * renderedFramesCount are not in it: the entry does not depend on them. (renderedFramesCount == 0 drops the cache
  * whatever the key says: primary_cache_decide.) */
 #ifndef WCPT_PRIMARY_CACHE_KEY_H
 #define WCPT_PRIMARY_CACHE_KEY_H

@@ -164,9 +164,9 @@ struct MkState {
     hipStream_t pipe[2] = {};  /* [1]: pipe 1's stream (pipe 0 runs on the context's stream) */
     hipEvent_t fork = nullptr;
     hipEvent_t join[2] = {};
-    /* Primary cache (WCPT_OPTION_PRIMARY_CACHE): per pixel of the context's rows the primary segment's Intersect record
-     * -- 8 B (t, primitive word) when the frame has one draw command, 12 B (+ draw) otherwise; a miss is (kInfinity,
-     * kNoPrim) -- tile-major like the costs above: record (ty * tilesX + tx) * 64 + lane. Written by the first render
+    /* Primary cache (WCPT_OPTION_PRIMARY_CACHE): per pixel of the context's rows the resolved primary segment
+     * (primary_record.h: direction, t with the facing bit, normal, material; 32 B, a miss is t = kInfinity),
+     * tile-major like the costs above: entry (ty * tilesX + tx) * 64 + lane. Written by the first render
      * after frame 0 of a still camera and read by the renders that follow while prim_key stands (primary_cache_key.h).
      * Independent of the kernel that fills it. */
     void* prim_mem = nullptr;

@@ -8,8 +8,8 @@
  * Instantiations: COUNT=false renders; COUNT=true runs the same frame without writing the image and counts the
  * reference algorithm's work; DIAG=true additionally counts SIMD lane/wave steps with a
  * __ballot inside the traversal loop (tools/diag.py only — kept out of the COUNT build the parity tests use).
- * The render builds come in three primary-cache modes (PC; pt_device.h intersect, primary_cache_key.h): none, write
- * (stores each pixel's primary Intersect record) and read (resolves the primary segment from it).
+ * The render builds come in three primary-cache modes (PC; pt_device.h TraceRay, primary_cache_key.h): none, write
+ * (stores each pixel's resolved primary segment, primary_record.h) and read (shades the primary segment from it).
  * mk_variant.h is the list of the instances: 96 render, 24 head (the first launch of a split render) and 16 counting
  * instances of pt_megakernel and 8 of pt_mk_tail; the dispatcher below (mk_dispatch) instantiates exactly those.
  */
@@ -102,7 +102,9 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
                                             const typename StageQueue<STAGE>::type& q)
 {
     const uint32_t x = lx, y = frame_row(rm, ly); /* the frame row: a row block or interleaved stripes (row_map.h) */
-    const f3 dir = primary_direction(sd, x, y, W, H);
+    /* a read build takes the direction from the pixel's cache entry (TraceRay) */
+    f3 dir = mk3(0.0f, 0.0f, 0.0f);
+    if constexpr (PC != kPrimCacheRead) dir = primary_direction(sd, x, y, W, H);
     const uint32_t pixel_index = x + y * W + sd.renderedFramesCount * 719393u; /* :304 */
     uint32_t seed = pcg_hash(pixel_index);
     /* The accumulation read (:314) is issued before the trace, so its HBM latency hides behind the segments
@@ -113,15 +115,12 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
     phase_mark(cnt, 0);
     f3 result = mk3(0.0f, 0.0f, 0.0f);
     const f3 origin = mk3(sd.position[0], sd.position[1], sd.position[2]);
-    float4 prim_rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f); /* sample 0's primary Intersect record */
-    if constexpr (PC == kPrimCacheRead) { /* ... as an earlier frame stored it: loaded beside the image read */
-        const uint32_t* const pl = prim_cache_lane<SINGLE>(pcache);
-        prim_rec.x = __uint_as_float(pl[0]);
-        prim_rec.y = __uint_as_float(pl[1]);
-        if (!SINGLE) prim_rec.z = __uint_as_float(pl[2]);
-    }
-    /* the one-sample read build (mk_variant.h mk_variant_select) has its sample count as a constant: the record then dies at its one
-     * use instead of staying live across a sample loop (intersect: 20 VGPRs) */
+    float4 prim_rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f); /* sample 0's primary Intersect record (sample reuse) */
+    /* the resolved primary segment as an earlier frame stored it (primary_record.h): loaded beside the image read. The
+     * sample-reuse read build loads it again for every sample instead of holding its 8 registers across the loop */
+    PrimEntry entry = {};
+    if constexpr (PC == kPrimCacheRead && !REUSE) entry = prim_cache_load(pcache);
+    /* the one-sample read build (mk_variant.h mk_variant_select) has its sample count as a constant */
     /* so has a head launch (STAGE; the runtime splits one-sample renders only) */
     const uint32_t samples = ((PC == kPrimCacheRead && !REUSE) || STAGE == kStageHead) ? 1u : sd.samples;
     bool appended = false; /* head: the path went to the tail's queue, and the tail stores this pixel */
@@ -131,23 +130,40 @@ __device__ __forceinline__ void shade_pixel(const wcpt_scene_data& sd, const wcp
         Ray r;
         r.origin = origin;
         r.direction = dir;
-        r.invDirection = rcp3(dir);
+        if constexpr (PC == kPrimCacheRead) {
+            r.invDirection = dir; /* neither is read (TraceRay) */
+            if constexpr (REUSE) {
+                /* through an opaque copy of the (wave-uniform) pointer: a plain load is loop-invariant, and the
+                 * compiler then hoists it and holds the 8 registers across the sample loop after all */
+                uint32_t* pc = pcache;
+                asm volatile("" : "+s"(pc));
+                entry = prim_cache_load(pc);
+            }
+        } else {
+            r.invDirection = rcp3(dir);
+        }
         if constexpr (STAGE == kStageHead)
             result = result + TraceRay<COUNT, DIAG, PAIRS, SINGLE, Stack, REUSE, PC, A, STAGE>(r, seed, sd, mats, spheres, draws, tri_records, stk, cnt, overflow,
                                                            s + 1u == samples, prim_rec, s > 0u, pcache, qp,
-                                                           (uint32_t)((size_t)ly * W + lx), &appended);
+                                                           (uint32_t)((size_t)ly * W + lx), &appended, &entry);
         else
             result = result + TraceRay<COUNT, DIAG, PAIRS, SINGLE, Stack, REUSE, PC, A>(r, seed, sd, mats, spheres, draws, tri_records, stk, cnt, overflow,
-                                                           s + 1u == samples, prim_rec, s > 0u, pcache);
+                                                           s + 1u == samples, prim_rec, s > 0u, pcache, nullptr, 0u, nullptr,
+                                                           &entry);
     }
     if constexpr (STAGE == kStageHead) {
         if (appended) return;
     }
-    if (PC == kPrimCacheWrite && REUSE) { /* this build (samples > 1) holds sample 0's record in prim_rec (TraceRay) */
-        uint32_t* const pl = prim_cache_lane<SINGLE>(pcache);
-        pl[0] = __float_as_uint(prim_rec.x);
-        pl[1] = __float_as_uint(prim_rec.y);
-        if (!SINGLE) pl[2] = __float_as_uint(prim_rec.z);
+    if constexpr (PC == kPrimCacheWrite && REUSE) {
+        /* this build (samples > 1) holds sample 0's Intersect record in prim_rec (intersect): the entry is resolve_hit
+         * of it and the primary ray once more -- the same function on the same bits as in sample 0's intersect */
+        Ray r;
+        r.origin = origin;
+        r.direction = dir;
+        r.invDirection = dir; /* not read */
+        const Hit h = resolve_hit<kShadeA<A>>(r, prim_rec.x, __float_as_uint(prim_rec.y), __float_as_uint(prim_rec.z),
+                                              spheres, draws, tri_records);
+        prim_cache_store(pcache, dir, h);
     }
     if (!COUNT) accumulate_store(sd, image, wire, wire_ch, wm, W, lx, ly, old, result);
     if (COUNT) cnt.pixels++;
@@ -186,9 +202,9 @@ __global__ __launch_bounds__(64, WCPT_MK_WAVES) void pt_megakernel(const wcpt_sc
     Counters cnt = {};
     phase_start(cnt);
     bool overflow = false;
-    /* the tile's primary-cache records (pt_device.h prim_cache_lane): wave-uniform, the lane's offset is added at the use */
+    /* the tile's primary-cache entries (primary_record.h): wave-uniform, the lane's offset is added at the use */
     uint32_t* const pcache = PC == kPrimCacheNone ? nullptr
-        : prim_cache + (size_t)(ty * tilesX + tx) * (64u * (SINGLE ? 2u : 3u));
+        : prim_cache + primary_record_word(ty * tilesX + tx, 0u);
     if (lx < W && ly < rows) {
         if constexpr (SK == 0) {
             uint64_t mem[kPrivateStack];
@@ -663,7 +679,7 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
     }
     if (pcmode == kPrimaryCacheWrite) {
         mk.prim_valid = false;
-        const uint64_t bytes = (uint64_t)tiles * 64ull * (a.sd.drawCommandCount == 1u ? 8ull : 12ull) /* pt_device.h prim_cache_lane */;
+        const uint64_t bytes = primary_record_bytes(tiles);
         if (bytes > mk.prim_bytes) {
             mk.prim_bytes = 0;
             e = mk_grow(mk, stream, mk.prim_mem, bytes);

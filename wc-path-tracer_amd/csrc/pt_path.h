@@ -102,9 +102,8 @@ __device__ __forceinline__ f3 TraceTail(PathState& ps, uint32_t& rng, const wcpt
     f3 L;
     float4 prim_rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     for (;;) {
-        const Hit h = intersect<false, false, PAIRS, SINGLE, Stack, kPrimCacheNone, A, true>(ps.ray, sd, spheres, draws, tri_records,
-                                                                                      stk, cnt, overflow, false, prim_rec,
-                                                                                      false, nullptr);
+        const Hit h = intersect<false, false, PAIRS, SINGLE, Stack, A, true>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
+                                                                      overflow, false, prim_rec, false);
         if (path_shade<kShadeA<A>>(ps, h, rng, sd, mats, L, true)) return L;
     }
 }
@@ -112,7 +111,12 @@ __device__ __forceinline__ f3 TraceTail(PathState& ps, uint32_t& rng, const wcpt
 /* pathTracer.comp:241-284. prim_rec: the primary segment's Intersect record (t, primitive, draw), written by the
  * first sample; reuse_primary: a later sample, whose primary segment reads it instead of tracing the same ray again
  * (intersect). STAGE == kStageHead: the loop ends before segment q->cut, and the lanes whose path is still alive there
- * append it to the queue (`pixel`: its image index) and return with `appended` set. */
+ * append it to the queue (`pixel`: its image index) and return with `appended` set.
+ * Primary cache (pt_traversal.h): a write build stores sample 0's resolved primary segment right after its intersect,
+ * where the direction and the Hit are in registers. A read build gets the pixel's entry instead of a direction
+ * (ray.direction and ray.invDirection are not read): segment 0 is path_shade on the entry's Hit, from the camera along
+ * the entry's direction, and has no intersect -- its half of the loop is peeled off, so nothing of the entry is
+ * loop-carried -- and no intersect of that kernel is a primary segment's. */
 template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, bool REUSE = false, int PC = kPrimCacheNone,
           int A = kArithExact, int STAGE = kStageWhole>
 __device__ __forceinline__ f3 TraceRay(Ray ray, uint32_t& rng, const wcpt_scene_data& sd,
@@ -121,22 +125,51 @@ __device__ __forceinline__ f3 TraceRay(Ray ray, uint32_t& rng, const wcpt_scene_
                                        const uint64_t* __restrict__ tri_records, Stack& stk,
                                        Counters& cnt, bool& overflow, bool lastSample, float4& prim_rec,
                                        bool reuse_primary, uint32_t* __restrict__ pcache = nullptr,
-                                       const SplitQueue* q = nullptr, uint32_t pixel = 0u, bool* appended = nullptr)
+                                       const SplitQueue* q = nullptr, uint32_t pixel = 0u, bool* appended = nullptr,
+                                       const PrimEntry* entry = nullptr)
 {
     PathState ps;
-    path_begin<A>(ps, ray.origin, ray.direction);
     f3 L;
     if constexpr (STAGE == kStageHead) L = mk3(0.0f, 0.0f, 0.0f); /* what an appending lane returns (not read) */
+    if constexpr (PC == kPrimCacheRead) {
+        /* path_begin without the direction's reciprocal: path_shade sets invDirection before an intersect reads it */
+        ps.ray.origin = ray.origin;
+        ps.ray.invDirection = mk3(0.0f, 0.0f, 0.0f);
+        ps.totalLight = mk3(0.0f, 0.0f, 0.0f);
+        ps.transmittance = mk3(1.0f, 1.0f, 1.0f);
+        ps.bounce = 0;
+        /* the loop below, entered at its path_shade with the entry's Hit: each turn shades segment `seg` and then
+         * intersects segment seg + 1, so the kernel holds one path_shade and one intersect as before */
+        Hit h = prim_entry_hit<kShadeA<A>>(*entry, ray.origin, ps.ray.direction);
+        for (uint32_t seg = 0;; seg++) {
+            const bool done = path_shade<kShadeA<A>>(ps, h, rng, sd, mats, L, lastSample);
+            phase_mark(cnt, 5);
+            if constexpr (STAGE == kStageHead) {
+                if (seg + 1u == q->cut) { /* wave-uniform, as seg is */
+                    split_append(*q, !done, ps, rng, pixel);
+                    *appended = !done;
+                    return L;
+                }
+            }
+            if (done) return L;
+            h = intersect<COUNT, DIAG, PAIRS, SINGLE, Stack, A, STAGE == kStageHead>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
+                                                                      overflow, false, prim_rec, false);
+        }
+    } else {
+    path_begin<A>(ps, ray.origin, ray.direction);
     /* segment counter of this sample: uniform across the wave's lanes (all start a sample together), so `primary`
      * (segment 0: origin = the camera) is a wave-uniform branch condition */
     for (uint32_t seg = 0;; seg++) {
-        /* primary-cache read: no segment is traced as a primary one, and segment 0 of every sample is the record's */
-        const bool primary = PC != kPrimCacheRead && seg == 0u;
-        const bool reuse = PC == kPrimCacheRead ? seg == 0u : REUSE && seg == 0u && reuse_primary;
-        /* the sample-reuse build keeps the record in prim_rec anyway: its write is the caller's, after sample 0 */
-        constexpr int PCI = (PC == kPrimCacheWrite && REUSE) ? kPrimCacheNone : PC;
-        const Hit h = intersect<COUNT, DIAG, PAIRS, SINGLE, Stack, PCI, A, STAGE == kStageHead>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
-                                                                      overflow, primary, prim_rec, reuse, pcache);
+        const bool primary = seg == 0u;
+        const bool reuse = REUSE && seg == 0u && reuse_primary;
+        const Hit h = intersect<COUNT, DIAG, PAIRS, SINGLE, Stack, A, STAGE == kStageHead>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
+                                                                      overflow, primary, prim_rec, reuse);
+        /* a traced primary segment: sample 0's. (The sample-reuse write build keeps the Intersect record in prim_rec
+         * anyway and stores from the caller, after its sample loop: with the store here this toolchain's register
+         * allocator crashes on that instance.) */
+        if constexpr (PC == kPrimCacheWrite && !REUSE) {
+            if (seg == 0u && !reuse_primary) prim_cache_store(pcache, ps.ray.direction, h);
+        }
         const bool done = path_shade<kShadeA<A>>(ps, h, rng, sd, mats, L, lastSample);
         phase_mark(cnt, 5);
         if constexpr (STAGE == kStageHead) {
@@ -147,6 +180,7 @@ __device__ __forceinline__ f3 TraceRay(Ray ray, uint32_t& rng, const wcpt_scene_
             }
         }
         if (done) return L;
+    }
     }
 }
 

@@ -11,6 +11,7 @@
 #include "pt_counters.h"
 #include "pt_geometry.h"
 #include "pt_math.h"
+#include "primary_record.h"
 
 namespace wcpt::dev {
 
@@ -461,32 +462,76 @@ __device__ __forceinline__ void tiny_walk(const Ray& ray, const DrawGeom& g, boo
  * the same too: the megakernel keeps sample 0's and later samples resolve their primary segment from it (render
  * builds for samples > 1 only, a separate instantiation -- keeping the record costs the one-sample kernel 20 VGPRs --
  * and never the COUNT build, which traces every segment as the reference does for the exact counters). */
-/* Primary cache (WCPT_OPTION_PRIMARY_CACHE): the same record kept from one frame to the next while camera, frame
- * geometry and scene stand still (primary_cache_key.h has the rule). Render builds only; PC is the launch's mode:
- * kPrimCacheWrite traces as usual and stores the lane's record after the primary segment of sample 0 at `pcache`
- * (t bits, primitive word, and the draw when the frame has several: 2 or 3 u32 per pixel, tile-major -- record index
- * (ty * tilesX + tx) * 64 + lane; `pcache` is the tile's first record, wave-uniform, so a wave touches one contiguous
- * run whatever the tile order or pipe; a miss is (kInfinity, kNoPrim)); kPrimCacheRead resolves the primary segment of every sample from the record the caller loaded
- * into prim_rec, and passes primary = false as a constant, so the primary-only leaf code (primary pair records, sign
- * pre-reject) is not in that kernel at all. */
+/* Primary cache (WCPT_OPTION_PRIMARY_CACHE): the resolved primary segment kept from one frame to the next while camera,
+ * frame geometry and scene stand still (primary_cache_key.h has the rule, primary_record.h the entry: the primary ray's
+ * direction and resolve_hit's result for it, eight u32 per pixel, tile-major, the same for one draw and for several).
+ * Render builds only; PC is the launch's mode: kPrimCacheWrite traces as usual and stores the lane's entry after the
+ * primary segment of sample 0 (TraceRay; `pcache` is the tile's first entry, wave-uniform, so a wave touches one
+ * contiguous run whatever the tile order or pipe; a miss has t = kInfinity); kPrimCacheRead never calls intersect for a
+ * primary segment: segment 0 of every sample is path_shade on the loaded entry (TraceRay), so neither the primary
+ * direction, its reciprocal, resolve_hit nor the primary-only leaf code (primary pair records, sign pre-reject) is in
+ * that kernel at all. */
 constexpr int kPrimCacheNone = 0, kPrimCacheWrite = 1, kPrimCacheRead = 2;
-/* the lane's record among its tile's */
-template <bool SINGLE>
+/* the lane's entry among its tile's */
 __device__ __forceinline__ uint32_t* prim_cache_lane(uint32_t* tile_records)
 {
-    return tile_records + (threadIdx.x & 63u) * (SINGLE ? 2u : 3u);
+    return tile_records + primary_record_word(0u, threadIdx.x);
 }
-template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, int PC = kPrimCacheNone, int A = kArithExact,
-          bool SPLIT = false>
+/* The entry of a resolved primary segment (direction `dir`, resolve_hit's `h`) and back; h.p is the reader's own
+ * axpy_a<A>(origin, dir, t), the expression resolve_hit ends with. Two 16-byte accesses per lane. */
+__device__ __forceinline__ void prim_cache_store(uint32_t* __restrict__ tile_records, f3 dir, const Hit& h)
+{
+    PrimaryRecord r;
+    r.dir[0] = __float_as_uint(dir.x);
+    r.dir[1] = __float_as_uint(dir.y);
+    r.dir[2] = __float_as_uint(dir.z);
+    r.normal[0] = __float_as_uint(h.normal.x);
+    r.normal[1] = __float_as_uint(h.normal.y);
+    r.normal[2] = __float_as_uint(h.normal.z);
+    r.t = __float_as_uint(h.t);
+    r.material = h.material;
+    r.hit = h.hit;
+    r.front = h.front;
+    uint32_t w[kPrimRecWords];
+    primary_record_pack(r, w);
+    uint4* const pl = reinterpret_cast<uint4*>(prim_cache_lane(tile_records));
+    pl[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    pl[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+struct PrimEntry { uint4 lo, hi; }; /* an entry as loaded: unpacked at its use, so nothing of it lives longer than it must */
+__device__ __forceinline__ PrimEntry prim_cache_load(const uint32_t* __restrict__ tile_records)
+{
+    const uint4* const pl = reinterpret_cast<const uint4*>(prim_cache_lane(const_cast<uint32_t*>(tile_records)));
+    PrimEntry e;
+    e.lo = pl[0];
+    e.hi = pl[1];
+    return e;
+}
+template <int A>
+__device__ __forceinline__ Hit prim_entry_hit(const PrimEntry& e, f3 origin, f3& dir)
+{
+    const uint32_t w[kPrimRecWords] = {e.lo.x, e.lo.y, e.lo.z, e.lo.w, e.hi.x, e.hi.y, e.hi.z, e.hi.w};
+    const PrimaryRecord r = primary_record_unpack(w);
+    dir = mk3(__uint_as_float(r.dir[0]), __uint_as_float(r.dir[1]), __uint_as_float(r.dir[2]));
+    Hit h;
+    h.t = __uint_as_float(r.t);
+    h.hit = r.hit;
+    h.front = r.front;
+    h.material = r.material;
+    h.normal = mk3(__uint_as_float(r.normal[0]), __uint_as_float(r.normal[1]), __uint_as_float(r.normal[2]));
+    h.p = axpy_a<A>(origin, dir, h.t); /* :205, resolve_hit's */
+    return h;
+}
+template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, int A = kArithExact, bool SPLIT = false>
 __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& sd, const wcpt_sphere* __restrict__ spheres,
                                          const wcpt_draw_command* __restrict__ draws,
                                          const uint64_t* __restrict__ tri_records, Stack& stk,
                                          Counters& cnt, bool& overflow, bool primary, float4& prim_rec,
-                                         bool reuse_primary, uint32_t* __restrict__ pcache = nullptr)
+                                         bool reuse_primary)
 {
     float rt = kInfinity;
     uint32_t prim = kNoPrim, primDraw = 0;
-    /* a later sample's primary segment, or under the primary cache's read mode every sample's (TraceRay) */
+    /* a later sample's primary segment */
     if (!COUNT && reuse_primary) {
         rt = prim_rec.x;
         prim = __float_as_uint(prim_rec.y);
@@ -599,12 +644,6 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
         }
     }
     if (!COUNT && primary && sd.samples > 1u) prim_rec = make_float4(rt, __uint_as_float(prim), __uint_as_float(primDraw), 0.0f);
-    if (!COUNT && PC == kPrimCacheWrite && primary && !reuse_primary) { /* a traced primary segment: sample 0's */
-        uint32_t* const pl = prim_cache_lane<SINGLE>(pcache);
-        pl[0] = __float_as_uint(rt);
-        pl[1] = prim;
-        if (!SINGLE) pl[2] = primDraw;
-    }
     if (COUNT && prim != kNoPrim) cnt.hits++;
     ref_segment_end<COUNT>(cnt);
     const Hit hit = resolve_hit<kShadeA<A>>(ray, rt, prim, primDraw, spheres, draws, tri_records);
