@@ -652,6 +652,21 @@ int      wcpt_profile_end(wcpt_context* ctx, double* kernel_ms_total, uint32_t* 
  * by the first call, grown on demand, freed by wcpt_destroy. */
 int      wcpt_bvh_build_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t vertex_count, wcpt_buffer indices,
                                uint32_t index_count, wcpt_buffer nodes, uint32_t* nodes_used);
+/* The binned-SAH BVH, built the same way: the arguments, the synchronous contract, the scratch ownership and the meaning
+ * for the runtime's caches are those of wcpt_bvh_build_device, and afterwards `indices` and nodes[0 .. *nodes_used) hold
+ * exactly the bytes wcpt_bvh_build_sah (below) produces from the same positions and the same starting index order.
+ * WCPT_ERROR_INVALID_ARGUMENT, with neither buffer written: everything wcpt_bvh_build_device refuses, and the inputs on
+ * which wcpt_bvh_build_sah's float-to-int conversion of a bin would be undefined or which it would sort -- differences
+ * from wcpt_bvh_build_sah, which accepts them:
+ *   - a triangle whose centroid 0.5f * (min + max) is not finite on some axis (|min + max| overflows binary32);
+ *   - a node of two or more triangles whose centroid extent on some axis is positive and not finite, or so small
+ *     (below about 4.7e-38) that 16.f / extent is not finite;
+ *   - a node of more than 8 triangles with a positive centroid extent in which no split has a finite cost (its box's
+ *     extent overflows binary32, so every area is inf or NaN): the host builder falls back to a sort by centroid there.
+ * Scratch: about 350 bytes per triangle, shared with wcpt_bvh_build_device, plus 1536 bytes per node of two or more
+ * triangles on the level that has most of them (at most index_count / 6 nodes). */
+int      wcpt_bvh_build_sah_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t vertex_count, wcpt_buffer indices,
+                                   uint32_t index_count, wcpt_buffer nodes, uint32_t* nodes_used);
 
 /* ---- host utilities (no GPU needed) ----------------------------------------------------------------- */
 /* OBJ text -> unique (v,vt,vn) vertices + fan-triangulated indices (ModelLoader.jai:60-141). */

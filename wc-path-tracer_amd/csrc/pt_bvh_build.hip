@@ -196,10 +196,7 @@ hipError_t launch_step(const BvhBuild& b, uint32_t n, uint32_t level, hipStream_
 /* the prefix sums of in[0 .. ntri] into b.scan / b.scan_off (bvh_scan_at) */
 hipError_t launch_scan(const BvhBuild& b, const uint32_t* in, hipStream_t stream)
 {
-    const uint32_t nb = scan_blocks(b.ntri);
-    hipLaunchKernelGGL(dev::bvh_scan_blocks_kernel, dim3(nb), dim3(dev::kBvhBlock), 0, stream, in, b.ntri + 1u, b.scan, b.scan_off);
-    if (nb > 1u) hipLaunchKernelGGL(dev::bvh_scan_offsets_kernel, dim3(1), dim3(dev::kBvhBlock), 0, stream, b.scan_off, nb);
-    return hipGetLastError();
+    return bvh_launch_scan(in, b.ntri + 1u, b.scan, b.scan_off, stream);
 }
 
 hipError_t read_ctrl(const BvhBuild& b, uint32_t ctrl[kBvhCtrlWords], hipStream_t stream)
@@ -209,6 +206,14 @@ hipError_t read_ctrl(const BvhBuild& b, uint32_t ctrl[kBvhCtrlWords], hipStream_
 }
 
 } // namespace
+
+hipError_t bvh_launch_scan(const uint32_t* in, uint32_t n, uint32_t* scan, uint32_t* off, hipStream_t stream)
+{
+    const uint32_t nb = (uint32_t)(((uint64_t)n + (1u << kBvhScanShift) - 1u) >> kBvhScanShift);
+    hipLaunchKernelGGL(dev::bvh_scan_blocks_kernel, dim3(nb), dim3(dev::kBvhBlock), 0, stream, in, n, scan, off);
+    if (nb > 1u) hipLaunchKernelGGL(dev::bvh_scan_offsets_kernel, dim3(1), dim3(dev::kBvhBlock), 0, stream, off, nb);
+    return hipGetLastError();
+}
 
 uint64_t bvh_build_scratch_bytes(uint32_t index_count)
 {

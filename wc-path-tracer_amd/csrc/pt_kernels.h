@@ -228,6 +228,18 @@ hipError_t launch_composite_bloom(const float4* img, uint32_t width, uint32_t he
 uint64_t bvh_build_scratch_bytes(uint32_t index_count);
 hipError_t bvh_build_device(const float* vertices, uint32_t vertex_count, uint32_t* indices, uint32_t index_count,
                             void* nodes, void* scratch, uint32_t* status, uint32_t* nodes_used, hipStream_t stream);
+/* The exclusive prefix sums of in[0 .. n), n >= 1, as bvh_midpoint.h's bvh_scan_at reads them: scan[i] within i's block
+ * of 1 << kBvhScanShift elements, off[block] the blocks' offsets (one word per block). */
+hipError_t bvh_launch_scan(const uint32_t* in, uint32_t n, uint32_t* scan, uint32_t* off, hipStream_t stream);
+/* wcpt_bvh_build_sah_device (pt_bvh_sah.hip; the rule in bvh_sah.h): the binned-SAH BVH of wcpt_bvh_build_sah, with the
+ * arguments and the contract of bvh_build_device. `scratch` holds bvh_sah_scratch_bytes(index_count) bytes; *bins
+ * (*bins_bytes bytes, hipMalloc'ed, may be null) holds the bins of a level's open nodes and is replaced by a larger
+ * allocation when a level needs one. *status may also hold bvh_sah.h kSahCentroidNotFinite / kSahBadScale /
+ * kSahNoFiniteCost. */
+uint64_t bvh_sah_scratch_bytes(uint32_t index_count);
+hipError_t bvh_build_sah_device(const float* vertices, uint32_t vertex_count, uint32_t* indices, uint32_t index_count,
+                                void* nodes, void* scratch, void** bins, uint64_t* bins_bytes, uint32_t* status,
+                                uint32_t* nodes_used, hipStream_t stream);
 /* overlap: WCPT_OPTION_FRAME_OVERLAP as the runtime allows it for this render (0 off, 1 auto, 2 on whenever the tiles
  * are cost-ordered); with 0 a pending overlap is joined first and the frame runs on `stream` */
 hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkState& mk, hipStream_t stream,

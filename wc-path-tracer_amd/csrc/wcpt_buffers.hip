@@ -4,7 +4,7 @@
  * which writes two of the context's buffers.
  */
 #include "wcpt_context.h"
-#include "bvh_midpoint.h"
+#include "bvh_sah.h"
 
 using namespace wcpt::rt;
 
@@ -50,6 +50,66 @@ void shadow_mark(Buffer& b, uint64_t offset, uint64_t end)
 void shadow_forget(Buffer& b, uint64_t offset, uint64_t end)
 {
     for (uint64_t c = offset / kShadowChunk; c < (end + kShadowChunk - 1) / kShadowChunk && c < b.known.size(); c++) b.known[c] = 0;
+}
+
+/* wcpt_bvh_build_device and wcpt_bvh_build_sah_device: one set of argument checks, one scratch allocation (the two
+ * builds are synchronous, so they take turns in it), one way of telling the runtime's caches what was written */
+int bvh_build_on_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t vertex_count, wcpt_buffer indices,
+                        uint32_t index_count, wcpt_buffer nodes, uint32_t* nodes_used, bool sah)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    Buffer* bv = find_buffer(ctx, vertices);
+    Buffer* bi = find_buffer(ctx, indices);
+    Buffer* bn = find_buffer(ctx, nodes);
+    if (!bv || !bi || !bn) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: unknown buffer handle");
+    if (bv == bi || bv == bn || bi == bn) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: the three buffers must differ");
+    if (!nodes_used) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: null nodes_used");
+    if (index_count == 0 || index_count % 3 != 0)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: index_count %u is zero or no multiple of 3", index_count);
+    if ((uint64_t)vertex_count * 12ull > bv->bytes)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: %u vertices exceed the vertex buffer (%llu bytes)",
+                         vertex_count, (unsigned long long)bv->bytes);
+    if ((uint64_t)index_count * 4ull > bi->bytes)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: %u indices exceed the index buffer (%llu bytes)",
+                         index_count, (unsigned long long)bi->bytes);
+    const uint64_t node_bound = 2ull * index_count / 3ull;
+    if (bn->bytes / sizeof(wcpt_node) < node_bound)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: the node buffer holds %llu nodes, %llu needed",
+                         (unsigned long long)(bn->bytes / sizeof(wcpt_node)), (unsigned long long)node_bound);
+    const uint64_t need = sah ? wcpt::bvh_sah_scratch_bytes(index_count) : wcpt::bvh_build_scratch_bytes(index_count);
+    if (ctx->bvh_bytes < need) {
+        rc = grow(ctx, ctx->d_bvh, ctx->bvh_bytes, need, need, "hipMalloc(bvh build scratch)");
+        if (rc) return rc;
+    }
+    uint32_t status = 0, used = 0;
+    if (sah) {
+        HIP_TRY(ctx, wcpt::bvh_build_sah_device(static_cast<const float*>(bv->ptr), vertex_count, static_cast<uint32_t*>(bi->ptr),
+                                                index_count, bn->ptr, ctx->d_bvh, &ctx->d_bvh_bins, &ctx->bvh_bins_bytes, &status,
+                                                &used, ctx->stream), "bvh sah build");
+    } else {
+        HIP_TRY(ctx, wcpt::bvh_build_device(static_cast<const float*>(bv->ptr), vertex_count, static_cast<uint32_t*>(bi->ptr),
+                                            index_count, bn->ptr, ctx->d_bvh, &status, &used, ctx->stream), "bvh build");
+    }
+    if (status & wcpt::kBvhBadIndex)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: an index is not below vertex_count %u", vertex_count);
+    if (status & wcpt::kBvhNotFinite)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: a referenced coordinate is not finite");
+    if (status & wcpt::kSahCentroidNotFinite)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh sah build: a triangle's centroid 0.5f * (lo + hi) is not finite");
+    if (status & wcpt::kSahBadScale)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh sah build: a node's centroid extent, or 16 / extent, is not finite");
+    if (status & wcpt::kSahNoFiniteCost)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT,
+                         "bvh sah build: a node of more than 8 triangles has no finite split cost (its box overflows binary32)");
+    /* a write of both buffers, as wcpt_buffer_upload's: the host copies no longer know the range, and everything keyed
+     * on the generations (triangle records, leaf scan, tiny-tree flag, frame preparation, primary cache) is re-learned */
+    shadow_forget(*bi, 0, (uint64_t)index_count * 4ull);
+    shadow_forget(*bn, 0, (uint64_t)used * sizeof(wcpt_node));
+    bi->generation = ++ctx->generation;
+    bn->generation = ++ctx->generation;
+    *nodes_used = used;
+    return WCPT_SUCCESS;
 }
 
 } // namespace
@@ -181,50 +241,17 @@ int wcpt_buffer_free(wcpt_context* ctx, wcpt_buffer buf)
     return WCPT_SUCCESS;
 }
 
-/* ---- BVH build on the device (pt_bvh_build.hip) --------------------------------------------------- */
+/* ---- BVH build on the device (pt_bvh_build.hip, pt_bvh_sah.hip) ------------------------------------ */
 int wcpt_bvh_build_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t vertex_count, wcpt_buffer indices,
                           uint32_t index_count, wcpt_buffer nodes, uint32_t* nodes_used)
 {
-    int rc = bind(ctx);
-    if (rc) return rc;
-    Buffer* bv = find_buffer(ctx, vertices);
-    Buffer* bi = find_buffer(ctx, indices);
-    Buffer* bn = find_buffer(ctx, nodes);
-    if (!bv || !bi || !bn) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: unknown buffer handle");
-    if (bv == bi || bv == bn || bi == bn) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: the three buffers must differ");
-    if (!nodes_used) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: null nodes_used");
-    if (index_count == 0 || index_count % 3 != 0)
-        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: index_count %u is zero or no multiple of 3", index_count);
-    if ((uint64_t)vertex_count * 12ull > bv->bytes)
-        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: %u vertices exceed the vertex buffer (%llu bytes)",
-                         vertex_count, (unsigned long long)bv->bytes);
-    if ((uint64_t)index_count * 4ull > bi->bytes)
-        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: %u indices exceed the index buffer (%llu bytes)",
-                         index_count, (unsigned long long)bi->bytes);
-    const uint64_t node_bound = 2ull * index_count / 3ull;
-    if (bn->bytes / sizeof(wcpt_node) < node_bound)
-        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: the node buffer holds %llu nodes, %llu needed",
-                         (unsigned long long)(bn->bytes / sizeof(wcpt_node)), (unsigned long long)node_bound);
-    const uint64_t need = wcpt::bvh_build_scratch_bytes(index_count);
-    if (ctx->bvh_bytes < need) {
-        rc = grow(ctx, ctx->d_bvh, ctx->bvh_bytes, need, need, "hipMalloc(bvh build scratch)");
-        if (rc) return rc;
-    }
-    uint32_t status = 0, used = 0;
-    HIP_TRY(ctx, wcpt::bvh_build_device(static_cast<const float*>(bv->ptr), vertex_count, static_cast<uint32_t*>(bi->ptr),
-                                        index_count, bn->ptr, ctx->d_bvh, &status, &used, ctx->stream), "bvh build");
-    if (status & wcpt::kBvhBadIndex)
-        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: an index is not below vertex_count %u", vertex_count);
-    if (status & wcpt::kBvhNotFinite)
-        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh build: a referenced coordinate is not finite");
-    /* a write of both buffers, as wcpt_buffer_upload's: the host copies no longer know the range, and everything keyed
-     * on the generations (triangle records, leaf scan, tiny-tree flag, frame preparation, primary cache) is re-learned */
-    shadow_forget(*bi, 0, (uint64_t)index_count * 4ull);
-    shadow_forget(*bn, 0, (uint64_t)used * sizeof(wcpt_node));
-    bi->generation = ++ctx->generation;
-    bn->generation = ++ctx->generation;
-    *nodes_used = used;
-    return WCPT_SUCCESS;
+    return bvh_build_on_device(ctx, vertices, vertex_count, indices, index_count, nodes, nodes_used, false);
+}
+
+int wcpt_bvh_build_sah_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t vertex_count, wcpt_buffer indices,
+                              uint32_t index_count, wcpt_buffer nodes, uint32_t* nodes_used)
+{
+    return bvh_build_on_device(ctx, vertices, vertex_count, indices, index_count, nodes, nodes_used, true);
 }
 
 } /* extern "C" */

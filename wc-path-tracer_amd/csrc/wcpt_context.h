@@ -95,8 +95,10 @@ struct wcpt_context {
     uint32_t* d_scan = nullptr;        /* leaf-count scan flag (prepare_tri_records) */
     float4* d_bloom = nullptr;         /* wcpt_composite_bloom: the down pyramid, then the up pyramid (on first use) */
     uint64_t bloom_bytes = 0;
-    void* d_bvh = nullptr;             /* wcpt_bvh_build_device: its scratch (on first use, grown on demand) */
+    void* d_bvh = nullptr;             /* wcpt_bvh_build_device / _sah_device: their scratch (on first use, grown on demand) */
     uint64_t bvh_bytes = 0;
+    void* d_bvh_bins = nullptr;        /* wcpt_bvh_build_sah_device: the bins of a level's open nodes (grown on demand) */
+    uint64_t bvh_bins_bytes = 0;
     uint64_t scratch_bytes = 0;
     int kernel = WCPT_KERNEL_MEGAKERNEL;
     int kernel_run = WCPT_KERNEL_MEGAKERNEL; /* the variant the current/last render runs (WCPT_KERNEL_AUTO resolved) */

@@ -113,12 +113,17 @@ class Context:
             self.buffer_upload(b, a)
         return b
 
-    def bvh_build_device(self, vb: int, vertex_count: int, ib: int, index_count: int, nb: int) -> int:
+    def bvh_build_device(self, vb: int, vertex_count: int, ib: int, index_count: int, nb: int,
+                         builder: str = "midpoint") -> int:
         """wcpt_bvh_build_device: the midpoint BVH of the index buffer `ib` over the vertex buffer `vb`, built on the
         device into the node buffer `nb` (at least 2 * index_count / 3 nodes), `ib` permuted in place -- the bytes of
-        wcpt_bvh_build. Returns the node count."""
+        wcpt_bvh_build. With builder="sah", wcpt_bvh_build_sah_device: the bytes of wcpt_bvh_build_sah. Returns the
+        node count."""
+        if builder not in ("midpoint", "sah"):
+            raise ValueError(f"unknown BVH builder {builder!r}")
+        fn = lib.wcpt_bvh_build_device if builder == "midpoint" else lib.wcpt_bvh_build_sah_device
         used = C.c_uint32()
-        self._chk(lib.wcpt_bvh_build_device(self.h, vb, vertex_count, ib, index_count, nb, C.byref(used)))
+        self._chk(fn(self.h, vb, vertex_count, ib, index_count, nb, C.byref(used)))
         return used.value
 
     # -- image ----------------------------------------------------------------------------------------
@@ -387,6 +392,7 @@ class PathTracingRenderer:
         self.spheres = np.zeros(0, dtype=SPHERE_DTYPE)
         self.meshes = []
         self.build = "host"              # Init's `build`: where LoadModel builds each mesh's BVH
+        self.bvh = "midpoint"            # Init's `bvh`: which tree
         self.ctx = Context(device)
         if arith != ARITH_EXACT:
             self.ctx.set_option(OPTION_ARITH, arith)
@@ -394,18 +400,25 @@ class PathTracingRenderer:
         self._mesh_bufs = []
 
     # Init :272-343 — LoadModel + materials/spheres + UpdateMaterials
-    def Init(self, model_path: str | None = None, scene: "_scene.HostScene | None" = None, build: str = "host"):
+    def Init(self, model_path: str | None = None, scene: "_scene.HostScene | None" = None, build: str = "host",
+             bvh: str = "midpoint"):
         """build: "host" (default) uploads trees built by wcpt_bvh_build; "device" uploads each mesh's positions and
         indices as they are and builds the same tree there (wcpt_bvh_build_device), so a model is loaded without the
-        host builder's stall."""
+        host builder's stall.
+        bvh: "midpoint" (default, the reference's tree) or "sah", the binned-SAH tree: built by wcpt_bvh_build_sah on
+        the host or by wcpt_bvh_build_sah_device, from each mesh's positions and indices as they are (a `scene` whose
+        meshes carry nodes of their own has those nodes uploaded only with build="host", bvh="midpoint")."""
         if build not in ("host", "device"):
             raise ValueError(f"unknown build {build!r}")
+        if bvh not in ("midpoint", "sah"):
+            raise ValueError(f"unknown bvh {bvh!r}")
         self.build = build
+        self.bvh = bvh
         if scene is None:
             scene = _scene.generate("default")
             if model_path is not None:
                 mesh = _scene.obj_load(model_path)
-                scene.meshes = [mesh if build == "device" else _scene.bvh_build(mesh)]
+                scene.meshes = [mesh if build == "device" or bvh == "sah" else _scene.bvh_build(mesh)]
         self.materials = scene.materials.copy()
         self.spheres = scene.spheres.copy()
         self.meshes = list(scene.meshes)
@@ -417,8 +430,10 @@ class PathTracingRenderer:
         draws = np.zeros(len(self.meshes), dtype=DRAW_COMMAND_DTYPE)
         for i, m in enumerate(self.meshes):
             if self.build == "device":
-                vb, ib, nb, _ = _scene.device_bvh_build(self.ctx, _scene.HostMesh(m.positions, m.indices))
+                vb, ib, nb, _ = _scene.device_bvh_build(self.ctx, _scene.HostMesh(m.positions, m.indices), self.bvh)
             else:
+                if self.bvh == "sah":
+                    m = _scene.bvh_build(_scene.HostMesh(m.positions, m.indices), "sah")
                 vb, ib, nb = (self.ctx.buffer_from(m.positions), self.ctx.buffer_from(m.indices),
                               self.ctx.buffer_from(m.nodes))
             self._mesh_bufs += [vb, ib, nb]

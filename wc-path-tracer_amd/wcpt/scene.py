@@ -125,16 +125,19 @@ def bvh_build(mesh: HostMesh, builder: str = "midpoint") -> HostBVH:
     return HostBVH(pos, idx, nodes[: used.value].copy())
 
 
-def device_bvh_build(ctx, mesh: HostMesh):
-    """The midpoint BVH of `mesh` built on ctx's device (wcpt_bvh_build_device): uploads the positions and the
-    unpermuted indices, allocates 2 * triangles nodes and builds. Returns (vertex buffer, index buffer, node buffer,
-    nodes used): handles of ctx, holding the bytes bvh_build(mesh) would upload."""
+def device_bvh_build(ctx, mesh: HostMesh, builder: str = "midpoint"):
+    """The midpoint (or, with builder="sah", the binned-SAH) BVH of `mesh` built on ctx's device (wcpt_bvh_build_device,
+    wcpt_bvh_build_sah_device): uploads the positions and the unpermuted indices, allocates 2 * triangles nodes and
+    builds. Returns (vertex buffer, index buffer, node buffer, nodes used): handles of ctx, holding the bytes
+    bvh_build(mesh, builder) would upload."""
+    if builder not in ("midpoint", "sah"):
+        raise ValueError(f"unknown BVH builder {builder!r}")
     pos = np.ascontiguousarray(mesh.positions, dtype=np.float32)
     idx = np.ascontiguousarray(mesh.indices, dtype=np.uint32)
     vb, ib = ctx.buffer_from(pos), ctx.buffer_from(idx)
     nb = ctx.buffer_alloc(max(1, 2 * (idx.size // 3)) * NODE_DTYPE.itemsize)
     try:
-        used = ctx.bvh_build_device(vb, pos.shape[0], ib, idx.size, nb)
+        used = ctx.bvh_build_device(vb, pos.shape[0], ib, idx.size, nb, builder=builder)
     except Exception:
         for b in (vb, ib, nb):
             ctx.buffer_free(b)
