@@ -41,7 +41,8 @@ extern "C" {
  * 4: WCPT_GROUP_OPTION_THREADS (each local rank's share of a frame issued from a host thread of its own);
  *    wcpt_group_info gained issue_threads; wcpt_group_set_output reads `bytes` in every process. Later additions that
  *    keep the layouts and calls (no version step): WCPT_GROUP_TRANSPORT_DIRECT, WCPT_OPTION_PROFILE_REGION,
- *    WCPT_OPTION_WF_FETCH, WCPT_OPTION_WF_PIPES 0 (automatic, now the default). */
+ *    WCPT_OPTION_WF_FETCH, WCPT_OPTION_WF_PIPES 0 (automatic, now the default), wcpt_bvh_refit,
+ *    wcpt_bvh_refit_device. */
 #define WCPT_ABI_VERSION 4
 
 /* ---- error codes (VkResult-compatible where a VkResult exists) ---------------------------------- */
@@ -89,7 +90,9 @@ extern "C" {
  * 0: the draw commands are read from the device, the records rebuilt on every render and the fast leaf layout is not
  * used (use this when the application writes draw-command, vertex, index or BVH buffers by other means, e.g. hipMemcpy
  * to a wcpt_buffer_device_address, a refit or its own kernels: with 1, such writes into uploaded ranges are not
- * seen). A BVH rewritten behind the cache can give a wrong image but never a read outside the derived records. */
+ * seen). A BVH rewritten behind the cache can give a wrong image but never a read outside the derived records.
+ * The library's own refit is the exception: wcpt_bvh_refit_device counts as a write of the node AND the vertex buffer,
+ * so vertices written by other means followed by that call are seen with the option left at 1. */
 #define WCPT_OPTION_TRIANGLE_CACHE 5
 /* Megakernel leaf tests: -1 (default) choose by mean triangles per leaf; 0 single records; 1 pair records
  * (two triangles per lane with packed-FP32 arithmetic). Results are identical either way. */
@@ -667,6 +670,36 @@ int      wcpt_bvh_build_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t
  * triangles on the level that has most of them (at most index_count / 6 nodes). */
 int      wcpt_bvh_build_sah_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t vertex_count, wcpt_buffer indices,
                                    uint32_t index_count, wcpt_buffer nodes, uint32_t* nodes_used);
+/* Refit: the vertices moved, the triangles did not. The boxes of nodes[0 .. nodes_used) are recomputed on the device from
+ * the vertex buffer's current contents, bottom-up; the tree's shape -- leftNodeOrTriangleIndex, triangleCount, the index
+ * order, the node numbering -- is never written. A leaf's box is the fold of a < b ? a : b / a > b ? a : b over the
+ * vertices of its index range in index order from +-FLOAT32_MAX (the reference's UpdateNodeBounds), an interior node's
+ * the union of its children's with the left child as the first operand. Afterwards nodes[0 .. nodes_used) holds exactly
+ * the bytes wcpt_bvh_refit (below) produces; `nodes` past nodes_used, `indices` and `vertices` are untouched. Three
+ * distinct context buffers; synchronous on the context's stream, behind the frame-overlap pipes, like the builds. The
+ * tree may be either builder's or hand-made. Over unchanged positions a refit reproduces the builder's boxes in value,
+ * and in bits except that a bound that is a zero may change its sign (the builders resolve a +0 / -0 tie by an order of
+ * the triangles that the finished tree no longer holds).
+ * WCPT_ERROR_INVALID_ARGUMENT, with no byte of `nodes` changed and a message that names the reason: an unknown handle
+ * (or one buffer passed twice); vertex_count * 12, index_count * 4 or nodes_used * 32 beyond its buffer; nodes_used zero;
+ * and whatever is not a tree over these indices, found on the device by read-only passes --
+ *   - an interior node i (triangleCount 0) whose left child is not > i or whose right child left + 1 is not < nodes_used
+ *     (both builders number children after their parents);
+ *   - a node other than 0 that is not the child of exactly one interior node;
+ *   - a leaf whose triangleCount is no multiple of 3 or whose range left + triangleCount exceeds index_count;
+ *   - an index >= vertex_count anywhere in indices[0 .. index_count) (a pass that reads only the indices; no vertex is
+ *     read once it has found one);
+ *   - a coordinate a leaf references that is not finite.
+ * A refit never improves a tree. It keeps the partition the builder chose for the old positions: after a large
+ * deformation the boxes of siblings overlap and rays visit more nodes, with the same image. When to build anew
+ * (wcpt_bvh_build_device, wcpt_bvh_build_sah_device) is the application's decision.
+ * For the runtime's caches the call is a write of `nodes` AND of `vertices`, exactly as wcpt_buffer_upload of both. So an
+ * application may deform the vertices with a kernel of its own (or a hipMemcpy) at wcpt_buffer_device_address, call the
+ * refit and render with WCPT_OPTION_TRIANGLE_CACHE left at 1: the triangle records, the leaf scan, the tiny-tree flag,
+ * the frame preparation and the primary cache are all re-learned. Scratch: about 40 bytes per node, shared with the
+ * builds. */
+int      wcpt_bvh_refit_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t vertex_count, wcpt_buffer indices,
+                               uint32_t index_count, wcpt_buffer nodes, uint32_t nodes_used);
 
 /* ---- host utilities (no GPU needed) ----------------------------------------------------------------- */
 /* OBJ text -> unique (v,vt,vn) vertices + fan-triangulated indices (ModelLoader.jai:60-141). */
@@ -682,6 +715,11 @@ int      wcpt_bvh_build(const float* positions, uint32_t vertex_count, uint32_t*
  * the same t. Permutes `indices` into leaf order; 2*index_count/3 nodes always suffice. */
 int      wcpt_bvh_build_sah(const float* positions, uint32_t vertex_count, uint32_t* indices,
                             uint32_t index_count, wcpt_node* nodes, uint32_t max_nodes, uint32_t* nodes_used);
+/* The refit of wcpt_bvh_refit_device (above) on the host: the same rule, the same refusals (WCPT_ERROR_INVALID_ARGUMENT,
+ * no byte of `nodes` changed, the reason in wcpt_last_error(NULL)), the same bytes. It is the byte reference of the
+ * device path and the sensible choice for small meshes, where the device refit is bound by its launches. */
+int      wcpt_bvh_refit(const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
+                        wcpt_node* nodes, uint32_t nodes_used);
 /* Camera Update (PathTracingRenderer.jai:22-36): yaw/pitch/fov/position -> matrices. */
 int      wcpt_camera_update(wcpt_camera* cam, float aspect_ratio);
 /* Scene generators: "default" (reference Init scene, PathTracingRenderer.jai:322-339, without a mesh),

@@ -240,6 +240,14 @@ uint64_t bvh_sah_scratch_bytes(uint32_t index_count);
 hipError_t bvh_build_sah_device(const float* vertices, uint32_t vertex_count, uint32_t* indices, uint32_t index_count,
                                 void* nodes, void* scratch, void** bins, uint64_t* bins_bytes, uint32_t* status,
                                 uint32_t* nodes_used, hipStream_t stream);
+/* wcpt_bvh_refit_device (pt_bvh_refit.hip; the rule in bvh_refit.h): the boxes of nodes[0 .. nodes_used) recomputed
+ * from `vertices`, bottom-up, in `scratch` of bvh_refit_scratch_bytes(nodes_used) bytes. Blocks the host: *status is 0
+ * when the boxes were stored; else it holds bvh_refit.h kRefit* bits and nothing was written to `nodes`. Nothing but
+ * `nodes` and `scratch` is ever written; no vertex is read, and no index used as an address, unless every index is below
+ * vertex_count. */
+uint64_t bvh_refit_scratch_bytes(uint32_t nodes_used);
+hipError_t bvh_refit_device(const float* vertices, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
+                            void* nodes, uint32_t nodes_used, void* scratch, uint32_t* status, hipStream_t stream);
 /* overlap: WCPT_OPTION_FRAME_OVERLAP as the runtime allows it for this render (0 off, 1 auto, 2 on whenever the tiles
  * are cost-ordered); with 0 a pending overlap is joined first and the frame runs on `stream` */
 hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkState& mk, hipStream_t stream,

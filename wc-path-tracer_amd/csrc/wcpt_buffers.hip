@@ -1,10 +1,11 @@
 /*
  * wcpt_buffers.hip — C-ABI runtime, device buffers (BufferManager.jai): alloc / upload / download / free, the host
- * copies that let a render read its draw commands without a device round trip, and the BVH build on the device,
- * which writes two of the context's buffers.
+ * copies that let a render read its draw commands without a device round trip, and the BVH builds and the refit on
+ * the device, which write the context's buffers.
  */
 #include "wcpt_context.h"
 #include "bvh_sah.h"
+#include "bvh_refit.h"
 
 using namespace wcpt::rt;
 
@@ -252,6 +253,44 @@ int wcpt_bvh_build_sah_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t 
                               uint32_t index_count, wcpt_buffer nodes, uint32_t* nodes_used)
 {
     return bvh_build_on_device(ctx, vertices, vertex_count, indices, index_count, nodes, nodes_used, true);
+}
+
+/* ---- BVH refit on the device (pt_bvh_refit.hip) ------------------------------------------------------ */
+/* wcpt_bvh_refit_device: the builds' argument checks and scratch, what bvh_refit.h refuses, and the caches told of a
+ * write of the nodes and -- the reason to refit -- of the vertices, however those got into their buffer */
+int wcpt_bvh_refit_device(wcpt_context* ctx, wcpt_buffer vertices, uint32_t vertex_count, wcpt_buffer indices,
+                          uint32_t index_count, wcpt_buffer nodes, uint32_t nodes_used)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    Buffer* bv = find_buffer(ctx, vertices);
+    Buffer* bi = find_buffer(ctx, indices);
+    Buffer* bn = find_buffer(ctx, nodes);
+    if (!bv || !bi || !bn) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh refit: unknown buffer handle");
+    if (bv == bi || bv == bn || bi == bn) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh refit: the three buffers must differ");
+    if ((uint64_t)vertex_count * 12ull > bv->bytes)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh refit: %u vertices exceed the vertex buffer (%llu bytes)",
+                         vertex_count, (unsigned long long)bv->bytes);
+    if ((uint64_t)index_count * 4ull > bi->bytes)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh refit: %u indices exceed the index buffer (%llu bytes)",
+                         index_count, (unsigned long long)bi->bytes);
+    if (nodes_used == 0u || nodes_used > bn->bytes / sizeof(wcpt_node))
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh refit: nodes_used %u is zero or exceeds the node buffer (%llu nodes)",
+                         nodes_used, (unsigned long long)(bn->bytes / sizeof(wcpt_node)));
+    const uint64_t need = wcpt::bvh_refit_scratch_bytes(nodes_used);
+    if (ctx->bvh_bytes < need) {
+        rc = grow(ctx, ctx->d_bvh, ctx->bvh_bytes, need, need, "hipMalloc(bvh refit scratch)");
+        if (rc) return rc;
+    }
+    uint32_t status = 0;
+    HIP_TRY(ctx, wcpt::bvh_refit_device(static_cast<const float*>(bv->ptr), vertex_count, static_cast<const uint32_t*>(bi->ptr),
+                                        index_count, bn->ptr, nodes_used, ctx->d_bvh, &status, ctx->stream), "bvh refit");
+    if (status) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "bvh refit: %s", wcpt::refit_refusal(status));
+    shadow_forget(*bv, 0, (uint64_t)vertex_count * 12ull);
+    shadow_forget(*bn, 0, (uint64_t)nodes_used * sizeof(wcpt_node));
+    bv->generation = ++ctx->generation;
+    bn->generation = ++ctx->generation;
+    return WCPT_SUCCESS;
 }
 
 } /* extern "C" */

@@ -2,7 +2,7 @@
  * a call to the context's device and stream, and the one on-demand device allocation. Internal: not installed, not part
  * of the ABI. The parts:
  *   wcpt_runtime.hip  the context itself: create / destroy, options, queries, sync, profiling, the group's hooks
- *   wcpt_buffers.hip  device buffers and their host copies, the device BVH build's entry point
+ *   wcpt_buffers.hip  device buffers and their host copies, the device BVH builds' and refit's entry points
  *   wcpt_screen.hip   the image and which rows of the frame it holds (screen_layout.h), readback, the display step
  *   wcpt_render.hip   frame preparation (frame_prep.h), the render dispatch, the self-tests
  */
@@ -95,7 +95,7 @@ struct wcpt_context {
     uint32_t* d_scan = nullptr;        /* leaf-count scan flag (prepare_tri_records) */
     float4* d_bloom = nullptr;         /* wcpt_composite_bloom: the down pyramid, then the up pyramid (on first use) */
     uint64_t bloom_bytes = 0;
-    void* d_bvh = nullptr;             /* wcpt_bvh_build_device / _sah_device: their scratch (on first use, grown on demand) */
+    void* d_bvh = nullptr;             /* wcpt_bvh_build_device / _sah_device / wcpt_bvh_refit_device: their scratch (on first use, grown on demand) */
     uint64_t bvh_bytes = 0;
     void* d_bvh_bins = nullptr;        /* wcpt_bvh_build_sah_device: the bins of a level's open nodes (grown on demand) */
     uint64_t bvh_bins_bytes = 0;

@@ -109,6 +109,9 @@ int wcpt_runtime_version(int* version)
     return WCPT_SUCCESS;
 }
 
+/* host/wcpt_host.cpp: a host utility's refusal becomes the process's last error (not part of the ABI) */
+void wcpt_internal_note_error(const char* text) { set_error(nullptr, WCPT_ERROR_INVALID_ARGUMENT, "%s", text ? text : ""); }
+
 const char* wcpt_last_error(const wcpt_context* ctx)
 {
     if (ctx) return ctx->last_error.c_str();

@@ -20,6 +20,11 @@
 
 #include "../../include/wcpt.h"
 #include "../csrc/wcpt_bloom.h"
+#include "../csrc/bvh_refit.h"
+
+/* The runtime's last-error text (wcpt_runtime.hip), for the host utilities that name what they refuse. Weak: this file
+ * also links into stand-alone programs without the runtime, where the text is dropped. */
+extern "C" __attribute__((weak)) void wcpt_internal_note_error(const char* text);
 
 namespace {
 
@@ -948,6 +953,56 @@ int wcpt_bvh_build_sah(const float* positions, uint32_t vertex_count, uint32_t* 
         if (indices[i] >= vertex_count) return WCPT_ERROR_INVALID_ARGUMENT;
     try {
         return bvh_build_sah(positions, indices, index_count, nodes, max_nodes, nodes_used);
+    } catch (...) {
+        return WCPT_ERROR_OUT_OF_HOST_MEMORY;
+    }
+}
+
+namespace {
+
+int refit_refused(const char* what)
+{
+    if (wcpt_internal_note_error) {
+        char buf[256];
+        snprintf(buf, sizeof(buf), "bvh refit: %s", what);
+        wcpt_internal_note_error(buf);
+    }
+    return WCPT_ERROR_INVALID_ARGUMENT;
+}
+
+/* bvh_refit.h's checks, all of them before the first write; then the leaves' boxes as folded during the checks, the
+ * interior nodes' in one loop from the last node to the first (children come after their parents) */
+int bvh_refit(const float* pos, uint32_t vertex_count, const uint32_t* idx, uint32_t index_count, wcpt_node* nodes,
+              uint32_t nodes_used)
+{
+    using namespace wcpt;
+    std::vector<RefitBox> box(nodes_used);
+    std::vector<uint32_t> parent(nodes_used, kRefitNone), refs(nodes_used, 0u), depth(nodes_used), ctrl(kRefitCtrlWords, 0u);
+    const BvhRefit r{pos, vertex_count, idx, index_count, nodes, nodes_used, box.data(), parent.data(), refs.data(),
+                     depth.data(), ctrl.data()};
+    for (uint32_t i = 0; i < index_count; i++) refit_step_check_index(r, i);
+    for (uint32_t i = 0; i < nodes_used; i++) refit_step_node(r, i);
+    for (uint32_t i = 0; i < nodes_used; i++) refit_step_depth(r, i);
+    if (ctrl[kRefitCtrlStatus]) return refit_refused(refit_refusal(ctrl[kRefitCtrlStatus]));
+    for (uint32_t i = nodes_used; i-- > 0u;) {
+        if (!refit_is_leaf(nodes[i])) {
+            const uint32_t left = nodes[i].leftNodeOrTriangleIndex;
+            box[i] = refit_union(box[left], box[left + 1u]);
+        }
+        refit_step_store(r, i);
+    }
+    return WCPT_SUCCESS;
+}
+
+} // namespace
+
+int wcpt_bvh_refit(const float* positions, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
+                   wcpt_node* nodes, uint32_t nodes_used)
+{
+    if (!nodes || (!positions && vertex_count) || (!indices && index_count)) return refit_refused("null argument");
+    if (nodes_used == 0) return refit_refused("nodes_used is zero");
+    try {
+        return bvh_refit(positions, vertex_count, indices, index_count, nodes, nodes_used);
     } catch (...) {
         return WCPT_ERROR_OUT_OF_HOST_MEMORY;
     }

@@ -208,6 +208,8 @@ _PROTOTYPES = {
     "wcpt_bvh_build_sah": (_i, [_p, _u32, _p, _u32, _p, _u32, C.POINTER(_u32)]),
     "wcpt_bvh_build_device": (_i, [_p, _u64, _u32, _u64, _u32, _u64, C.POINTER(_u32)]),
     "wcpt_bvh_build_sah_device": (_i, [_p, _u64, _u32, _u64, _u32, _u64, C.POINTER(_u32)]),
+    "wcpt_bvh_refit": (_i, [_p, _u32, _p, _u32, _p, _u32]),
+    "wcpt_bvh_refit_device": (_i, [_p, _u64, _u32, _u64, _u32, _u64, _u32]),
     "wcpt_camera_update": (_i, [C.POINTER(Camera), C.c_float]),
     "wcpt_scene_generate": (_i, [C.c_char_p, _u32, C.POINTER(SceneC)]),
     "wcpt_scene_free": (None, [C.POINTER(SceneC)]),

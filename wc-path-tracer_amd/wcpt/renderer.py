@@ -13,7 +13,7 @@ import numpy as np
 
 from ._lib import (COUNTER_FIELDS, DRAW_COMMAND_DTYPE, GROUP_OPTION_ROW_STRIPE, GROUP_TRANSPORT_RCCL,
                    GROUP_UNIQUE_ID_BYTES, ARITH_EXACT, OPTION_ARITH, OPTION_DIAGNOSTICS,
-                   MATERIAL_DTYPE, SCENE_DATA_DTYPE, SPHERE_DTYPE, Camera, Counters, GroupInfo, WcptError, check, lib, ptr)
+                   MATERIAL_DTYPE, NODE_DTYPE, SCENE_DATA_DTYPE, SPHERE_DTYPE, Camera, Counters, GroupInfo, WcptError, check, lib, ptr)
 from . import scene as _scene
 
 
@@ -125,6 +125,11 @@ class Context:
         used = C.c_uint32()
         self._chk(fn(self.h, vb, vertex_count, ib, index_count, nb, C.byref(used)))
         return used.value
+
+    def bvh_refit_device(self, vb: int, vertex_count: int, ib: int, index_count: int, nb: int, nodes_used: int):
+        """wcpt_bvh_refit_device: the boxes of the first `nodes_used` nodes of `nb` recomputed on the device from the
+        vertex buffer's current contents -- the bytes of wcpt_bvh_refit; the tree's shape and `ib` are not written."""
+        self._chk(lib.wcpt_bvh_refit_device(self.h, vb, vertex_count, ib, index_count, nb, nodes_used))
 
     # -- image ----------------------------------------------------------------------------------------
     def create_screen(self, width: int, height: int):
@@ -398,6 +403,7 @@ class PathTracingRenderer:
             self.ctx.set_option(OPTION_ARITH, arith)
         self._mat_buf = self._sph_buf = self._draw_buf = None
         self._mesh_bufs = []
+        self._mesh_info = []             # per mesh: (vb, ib, nb, vertex count, index count, nodes used), for UpdateMesh
 
     # Init :272-343 — LoadModel + materials/spheres + UpdateMaterials
     def Init(self, model_path: str | None = None, scene: "_scene.HostScene | None" = None, build: str = "host",
@@ -428,20 +434,44 @@ class PathTracingRenderer:
     # LoadModel :219-270 — vertex/index/BVH uploads + one DrawCommand per mesh
     def LoadModel(self):
         draws = np.zeros(len(self.meshes), dtype=DRAW_COMMAND_DTYPE)
+        self._mesh_info = []
         for i, m in enumerate(self.meshes):
             if self.build == "device":
-                vb, ib, nb, _ = _scene.device_bvh_build(self.ctx, _scene.HostMesh(m.positions, m.indices), self.bvh)
+                vb, ib, nb, used = _scene.device_bvh_build(self.ctx, _scene.HostMesh(m.positions, m.indices), self.bvh)
             else:
                 if self.bvh == "sah":
                     m = _scene.bvh_build(_scene.HostMesh(m.positions, m.indices), "sah")
                 vb, ib, nb = (self.ctx.buffer_from(m.positions), self.ctx.buffer_from(m.indices),
                               self.ctx.buffer_from(m.nodes))
+                used = len(m.nodes)
             self._mesh_bufs += [vb, ib, nb]
+            self._mesh_info.append((vb, ib, nb, int(np.asarray(m.positions).reshape(-1, 3).shape[0]), int(m.indices.size), used))
             draws[i] = (self.ctx.buffer_address(vb), self.ctx.buffer_address(ib), self.ctx.buffer_address(nb),
                         m.indices.size, 0)
         if self._draw_buf is None:
             self._draw_buf = self.ctx.buffer_alloc(0)
         self.ctx.buffer_upload(self._draw_buf, draws)
+
+    def UpdateMesh(self, i: int, positions: np.ndarray, refit: str = "device"):
+        """New positions for mesh i, its triangles unchanged (an editor's drag, an animation's frame): uploads them,
+        refits that mesh's tree -- refit="device": wcpt_bvh_refit_device in place; "host": wcpt_bvh_refit over the
+        device's indices and nodes, uploaded back -- and restarts the accumulation, as the reference's editor does
+        whenever something moves. After Init with either `build` and either `bvh`."""
+        if refit not in ("device", "host"):
+            raise ValueError(f"unknown refit {refit!r}")
+        vb, ib, nb, vertex_count, index_count, used = self._mesh_info[i]
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        if pos.shape[0] != vertex_count:
+            raise ValueError(f"mesh {i} has {vertex_count} vertices, got {pos.shape[0]}")
+        if refit == "device":
+            _scene.device_bvh_refit(self.ctx, vb, ib, nb, pos, index_count, used)
+        else:
+            idx = np.frombuffer(self.ctx.buffer_download(ib, 4 * index_count), np.uint32)
+            nodes = np.frombuffer(self.ctx.buffer_download(nb, NODE_DTYPE.itemsize * used), NODE_DTYPE)
+            new = _scene.bvh_refit(_scene.HostBVH(pos, idx, nodes), pos)
+            self.ctx.buffer_upload(vb, pos)
+            self.ctx.buffer_upload(nb, new.nodes)
+        self.renderedFramesCount = 0
 
     # PushMaterial :492-496
     def PushMaterial(self) -> int:

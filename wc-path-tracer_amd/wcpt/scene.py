@@ -145,6 +145,26 @@ def device_bvh_build(ctx, mesh: HostMesh, builder: str = "midpoint"):
     return vb, ib, nb, used
 
 
+def bvh_refit(bvh: HostBVH, positions: np.ndarray) -> HostBVH:
+    """wcpt_bvh_refit: `bvh` with its boxes recomputed for `positions` (the same vertex count is not required, only that
+    every index stays below it); the tree's shape and the index order are kept. Returns a new HostBVH; `bvh` is not
+    modified."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(bvh.indices, dtype=np.uint32)
+    nodes = np.array(bvh.nodes, dtype=NODE_DTYPE, copy=True)
+    check(lib.wcpt_bvh_refit(ptr(pos) if pos.size else None, pos.shape[0], ptr(idx) if idx.size else None, idx.size,
+                             ptr(nodes) if nodes.size else None, nodes.size))
+    return HostBVH(pos.copy(), idx.copy(), nodes)
+
+
+def device_bvh_refit(ctx, vb: int, ib: int, nb: int, positions: np.ndarray, index_count: int, nodes_used: int):
+    """Uploads `positions` into the vertex buffer `vb`, then refits the tree in `nb` over the index buffer `ib` on ctx's
+    device (wcpt_bvh_refit_device)."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    ctx.buffer_upload(vb, pos)
+    ctx.bvh_refit_device(vb, pos.shape[0], ib, index_count, nb, nodes_used)
+
+
 def update_camera(cam: Camera, aspect: float) -> Camera:
     c = Camera()
     C.pointer(c)[0] = cam
