@@ -91,6 +91,11 @@ extern "C" {
  * used (use this when the application writes draw-command, vertex, index or BVH buffers by other means, e.g. hipMemcpy
  * to a wcpt_buffer_device_address, a refit or its own kernels: with 1, such writes into uploaded ranges are not
  * seen). A BVH rewritten behind the cache can give a wrong image but never a read outside the derived records.
+ * Vertex or index buffers the context does not know (addresses that are no wcpt_buffer of this context): with 1 their
+ * records are never kept from one frame preparation to the next, but a render that reuses the preparation of the render
+ * before -- draw commands uploaded to this context, and no wcpt_buffer_alloc / _upload / _free or option change on it
+ * since -- renders the records of that render, so writes into such buffers are not seen until one of those calls; with
+ * draw commands the context reads from the device every render prepares anew.
  * The library's own refit is the exception: wcpt_bvh_refit_device counts as a write of the node AND the vertex buffer,
  * so vertices written by other means followed by that call are seen with the option left at 1. */
 #define WCPT_OPTION_TRIANGLE_CACHE 5
@@ -284,7 +289,11 @@ typedef struct wcpt_node {
  * it derives the triangle records from index positions [0, indexCount), so indexCount must not exceed the index
  * buffer (checked for context buffers: wcpt_render returns WCPT_ERROR_INVALID_ARGUMENT), and vertex indices past a
  * context vertex buffer give a triangle that is never hit. Write draw commands through wcpt_buffer_upload, or see
- * WCPT_OPTION_TRIANGLE_CACHE. */
+ * WCPT_OPTION_TRIANGLE_CACHE.
+ * Each address may lie anywhere inside a context buffer (a sub-allocation of an arena, a second mesh stored behind the
+ * first), subject to its alignment: bvhBuffer a multiple of 16 bytes (the kernels load a node as two 16-byte rows),
+ * vertexBuffer and indexBuffer multiples of 4 (positions and indices are read as 32-bit words, a position as three of
+ * them). The bounds above then count from the address to the end of its buffer. */
 typedef struct wcpt_draw_command {
     uint64_t vertexBuffer;          /* -> float[3] positions, stride 12 */
     uint64_t indexBuffer;           /* -> uint32 indices (BVH-permuted) */
