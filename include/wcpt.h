@@ -190,10 +190,10 @@ extern "C" {
  * fewer -- is walked without the traversal loop: the wave reads the nodes through the scalar cache and tests the
  * leaves in the reference's order, with the reference's box tests and culls per lane (csrc/mk_tiny_rule.h has the
  * rule). A wave whose lanes disagree on the children's order tests the leaves in both orders, each for its own
- * lanes. -1 (default): automatic -- wherever the rule allows; 0: never; 1: wherever the rule allows. The walk is
- * compiled into the two launches of a split render only (WCPT_OPTION_MK_SPLIT: by itself the large one-sample frames
- * of scenes of at most 64 triangles, or a forced cut), so a render in one launch -- a small frame, samples > 1,
- * every larger mesh -- runs the kernel it ran before. Further only where the draw takes pair records
+ * lanes. -1 (default): automatic -- wherever the rule allows; 0: never; 1: wherever the rule allows. The walk has
+ * kernels of its own, which take the places of the two launches of a split render (WCPT_OPTION_MK_SPLIT: by itself
+ * the large one-sample frames of scenes of at most 64 triangles, or a forced cut), so a render in one launch -- a
+ * small frame, samples > 1, every larger mesh -- runs the kernel it ran before. Further only where the draw takes pair records
  * (WCPT_OPTION_PAIR_RECORDS: by itself from 4 triangles per leaf up, so the Cornell room does and a mesh of a few
  * triangles does not unless the option is 1), only in WCPT_ARITH_EXACT (the fast-arithmetic kernels keep the loop)
  * and only while WCPT_OPTION_TRIANGLE_CACHE is 1 (the tree is classified once per BVH buffer generation). Values
@@ -499,7 +499,7 @@ int      wcpt_primary_cache_stats(wcpt_context* ctx, uint64_t* writes, uint64_t*
 /* How many renders of the context ran as two launches (WCPT_OPTION_MK_SPLIT) since it was created. Host only. Added
  * under ABI 4. */
 int      wcpt_mk_split_stats(wcpt_context* ctx, uint64_t* renders);
-/* How many renders of the context ran on the instances that walk a tiny tree, with the draw's tree classified as one
+/* How many renders of the context ran on the kernels that walk a tiny tree, with the draw's tree classified as one
  * (WCPT_OPTION_MK_TINY_TREE), since it was created: a count of renders that selected the walk, not of waves. Host only. Added under ABI 4. */
 int      wcpt_mk_tiny_tree_stats(wcpt_context* ctx, uint64_t* renders);
 /* Same frame through the instrumented kernel: counts the reference algorithm's work.

@@ -1,7 +1,7 @@
 """Per-launch durations of a kernel in a rocprofv3 --kernel-trace CSV, in dispatch order, with the idle gap before each
 launch: shows whether the first frames after an idle host sync run slower than the steady ones.
 
-    python tools/launch_durations.py <dir with *kernel_trace.csv> [--kernel pt_megakernel<false] [--last 40]
+    python tools/launch_durations.py <dir with *kernel_trace.csv> [--kernel pt_megakernel<false,pt_mk_tail<,pt_tiny_head<,pt_tiny_tail] [--last 40]
 """
 import argparse
 import csv
@@ -12,14 +12,15 @@ import os
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("dir")
-    ap.add_argument("--kernel", default="pt_megakernel<false")
+    ap.add_argument("--kernel", default="pt_megakernel<false,pt_mk_tail<,pt_tiny_head<,pt_tiny_tail",
+                    help="comma list of kernel name parts: a launch of any of them counts")
     ap.add_argument("--last", type=int, default=40)
     a = ap.parse_args()
     rows = []
     for f in glob.glob(os.path.join(a.dir, "**", "*kernel_trace.csv"), recursive=True):
         rows += [r for r in csv.DictReader(open(f))]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    ks = [r for r in rows if a.kernel in r["Kernel_Name"]]
+    ks = [r for r in rows if any(f in r["Kernel_Name"] for f in a.kernel.split(","))]
     prev_end = None
     out = []
     for r in ks:

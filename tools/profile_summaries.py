@@ -18,7 +18,9 @@ from collections import defaultdict
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # per config: (kernel id, dominant-kernel filter, launches of it per frame, bound, resource, whole-frame PMC filters)
 SPEC = {
-    "c2": (0, "pt_megakernel<false", 1.0, "valu_issue",
+    # c2's frames are a tiny tree's split renders (csrc/pt_mk_tiny.hip): pt_tiny_head and pt_tiny_tail; with
+    # WCPT_OPTION_MK_TINY_TREE at 0 the general pair, a pt_megakernel head and pt_mk_tail. Head and tail are one frame
+    "c2": (0, "pt_megakernel<false,pt_mk_tail<,pt_tiny_head<,pt_tiny_tail", 1.0, "valu_issue",
            "VALU issue (SQ_INSTS_VALU x 2 cycles over the SIMD cycles of the launch; the mix-weighted ceiling in "
            "profiles/valu_mix_c2.json)", None),
     "ref": (0, "pt_megakernel<false", 1.0, "valu_issue",
@@ -35,7 +37,9 @@ MIX = ("ADD_F32", "MUL_F32", "FMA_F32", "TRANS_F32", "INT32", "INT64", "CVT")
 # megakernel work-items per frame (8x8 tiles x 64 lanes of the 1920x1080 frame): under the frame overlap
 # (WCPT_OPTION_FRAME_OVERLAP) a frame is two launches of half the tiles (and one around each re-sort), so the megakernel
 # summaries count per frame by grid and time the frame as the union of its launches' intervals (frame_ms)
-FRAME_GRID = {"c2": 240 * 135 * 64, "ref": 240 * 135 * 64}
+# c2 renders split (mk_split_rule.h): a frame is a head over its tiles and a tail over the queue's capacity, which is the
+# head's lanes -- twice the frame's work-items in all
+FRAME_GRID = {"c2": 2 * 240 * 135 * 64, "ref": 240 * 135 * 64}
 # wavefront pipelines per frame (one wf_init each: the per-frame divisor of the PMC passes). The library picks them by
 # queue length (WCPT_OPTION_WF_PIPES 0): 3 for the 1080p atrium (2.1 M paths, 4 per resident trace lane), 2 at 4K
 PIPES = {"c3": 3, "c4": 2}
@@ -44,7 +48,7 @@ PIPES = {"c3": 3, "c4": 2}
 def kernel_ms(d, cfg, filt):
     for f in glob.glob(os.path.join(d, f"prof_{cfg}", "**", "*kernel_stats.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
-            if filt in row["Name"]:
+            if any(f in row["Name"] for f in filt.split(",")):
                 return float(row["AverageNs"]) / 1e6
     raise SystemExit(f"{cfg}: no {filt} in the kernel stats")
 
@@ -56,7 +60,7 @@ def frame_ms(d, cfg, filt, frame_grid):
     iv, work = [], 0.0
     for f in glob.glob(os.path.join(d, f"prof_{cfg}", "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
-            if filt in row["Kernel_Name"]:
+            if any(f in row["Kernel_Name"] for f in filt.split(",")):
                 iv.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"])))
                 work += float(row["Grid_Size_X"]) * float(row.get("Grid_Size_Y") or 1) * float(row.get("Grid_Size_Z") or 1)
     if not iv:
@@ -77,7 +81,7 @@ def counters(d, cfg, filt):
     per = defaultdict(list)
     for f in glob.glob(os.path.join(d, f"sq_{cfg}", "p*", "**", "*counter_collection.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
-            if filt in row.get("Kernel_Name", ""):
+            if any(f in row.get("Kernel_Name", "") for f in filt.split(",")):
                 per[row["Counter_Name"]].append(float(row["Counter_Value"]))
     return {k: sum(v) / len(v) for k, v in per.items()}, {k: len(v) for k, v in per.items()}
 

@@ -33,7 +33,7 @@ constexpr uint64_t kTriFlagLeafRecords = 8u; /* table word 3: every leaf starts 
                                                 single record p / 3 (byte offset 16 p) */
 constexpr uint64_t kTriFlagTinyTree = 16u;  /* table word 3: the BVH is a root leaf or a root over two leaves, each on
                                                 derived records (mk_tiny_rule.h), and WCPT_OPTION_MK_TINY_TREE allows the
-                                                walk without the traversal loop (tiny_walk) */
+                                                walk without the traversal loop (pt_tiny.h tiny_walk) */
 /* the wavefront trace's one-draw fast layout: packed stack refs, 24-bit record offsets, buffer-resource node loads */
 constexpr uint64_t kTriFlagsFastLayout = kTriFlagPackedRefs | kTriFlagIndex24 | kTriFlagSmallLeaves | kTriFlagLeafRecords;
 

@@ -22,7 +22,7 @@
 #include "pt_geometry.h"  /* rays, nodes, box / sphere / triangle tests, triangle records */
 #include "pt_counters.h"  /* counters, RefStack, phase timers, WCPT_DUP_* */
 #include "pt_stacks.h"    /* PrivateStack, LdsStack */
-#include "pt_traversal.h" /* DrawGeom, the traversal steps, the tiny walk, intersect, resolve_hit */
+#include "pt_traversal.h" /* DrawGeom, the traversal steps, intersect, resolve_hit */
 #include "pt_shading.h"   /* CalculateReflectance, PathState, path_shade */
 #include "pt_path.h"      /* SplitQueue, TraceTail, TraceRay, primary_direction, store_pixel */
 

@@ -183,7 +183,7 @@ struct MkState {
     uint32_t* split_ctr = nullptr;            /* [pipe][2][kMkSplitCounterWords] */
     uint32_t split_parity[2] = {0u, 0u};
     uint64_t split_renders = 0;               /* renders that ran as head + tail (wcpt_mk_split_stats) */
-    uint64_t tiny_renders = 0;                /* renders whose instances walked a tiny tree (wcpt_mk_tiny_tree_stats) */
+    uint64_t tiny_renders = 0;                /* renders on the walk-only kernels (mk_tiny_kernels; wcpt_mk_tiny_tree_stats) */
 };
 constexpr uint32_t kMkPipes = 2;
 void mk_release(MkState& mk);

@@ -12,6 +12,10 @@
  * (stores each pixel's resolved primary segment, primary_record.h) and read (shades the primary segment from it).
  * mk_variant.h is the list of the instances: 96 render, 24 head (the first launch of a split render) and 16 counting
  * instances of pt_megakernel and 8 of pt_mk_tail; the dispatcher below (mk_dispatch) instantiates exactly those.
+ * Four more kernels are no instances of these and live in pt_mk_tiny.hip: pt_tiny_head<PC none / write / read> and
+ * pt_tiny_tail, the head and the tail of a split render whose one draw has a tiny tree (mk_tiny_rule.h
+ * mk_tiny_kernels), which hold the tiny-tree walk and nothing of the traversal loop; launch_megakernel takes them in the
+ * places of the head and tail that mk_variant_select chose. The kernels here hold nothing of the walk.
  */
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -21,73 +25,11 @@
 #include "mk_tiny_rule.h"
 #include "pt_device.h"
 #include "pt_kernels.h"
+#include "pt_mk_tile.h"
+#include "pt_mk_tiny.h"
 
 namespace wcpt {
 namespace dev {
-
-/* Pixel tile of one wave64: kTileW x kTileH. Measured on c2: 8x8 and 4x16 equal, 16x4 +3%, 32x2 +4%. */
-#ifndef WCPT_TILE_W
-#define WCPT_TILE_W 8
-#endif
-constexpr uint32_t kTileW = WCPT_TILE_W, kTileH = 64u / WCPT_TILE_W;
-
-/* Pixel tile -> block mapping. Blocks are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md,
- * "Workgroup dispatch"); remapping the linear block id so that each XCD walks a contiguous band of tiles
- * keeps neighbouring (coherent) tiles on one XCD's L2. Speed only; any placement is correct. */
-__device__ __forceinline__ void tile_of_block(uint32_t tilesX, uint32_t tilesTotal, uint32_t scatter,
-                                              const uint32_t* __restrict__ order, uint32_t& tx, uint32_t& ty)
-{
-    const uint32_t b = blockIdx.x;
-    uint32_t t = b;
-    if (order != nullptr) {
-        t = order[b]; /* cost-ordered: a permutation of [0, tilesTotal), longest tile first */
-    } else if (scatter & 1u) {
-        t = (uint32_t)(((uint64_t)b * scatter) % tilesTotal);   /* odd: scattered, multiplier `scatter` */
-    } else if ((tilesTotal & 7u) == 0u) {
-        /* blocks go to the XCDs round-robin (block b -> XCD b mod 8): XCD x walks the x-th eighth of a tile list */
-        t = (b & 7u) * (tilesTotal >> 3) + (b >> 3);
-        if (scatter != 0u) {
-            /* even scatter = 2h: striped list. Stripes of h tile rows, listed by (stripe mod 8, stripe / 8), each in
-             * raster order, so XCD x walks (about) the stripes s = x mod 8: neighbouring tiles stay together on an
-             * XCD, and every XCD sees every part of the frame (one contiguous band per XCD can leave a few XCDs with
-             * the heavy regions of the image) */
-            const uint32_t h = scatter >> 1;
-            const uint32_t tilesY = tilesTotal / tilesX;
-            const uint32_t full = tilesY / (8u * h), rem = tilesY % (8u * h);
-            for (uint32_t j = 0; j < 8u; j++) {
-                const uint32_t part = rem > j * h ? min(rem - j * h, h) : 0u;
-                const uint32_t seg = (full * h + part) * tilesX;   /* tiles of the rows in stripes s = j mod 8 */
-                if (t < seg) {
-                    const uint32_t lr = t / tilesX;
-                    t = (((lr / h) * 8u + j) * h + lr % h) * tilesX + t % tilesX;
-                    break;
-                }
-                t -= seg;
-            }
-        }
-    }
-    tx = t % tilesX;
-    ty = t / tilesX;
-}
-
-/* The end of a pixel (pathTracer.comp:312-323): the mean of the samples' radiance `result`, accumulated into the
- * image's value `old` (read early by the caller) and stored. Shared by the whole kernel, the head and the tail. */
-__device__ __forceinline__ void accumulate_store(const wcpt_scene_data& sd, float4* __restrict__ image,
-                                                 float* __restrict__ wire, uint32_t wire_ch, const RowMap& wm, uint32_t W,
-                                                 uint32_t lx, uint32_t ly, float4 old, f3 result)
-{
-    result = result / (float)sd.samples; /* :312 */
-    f3 acc;
-    if (sd.renderedFramesCount == 0) { /* :318 — the loaded value would be discarded */
-        acc = result;
-    } else {
-        const float4 o = old;                                             /* :314 */
-        const float weight = 1.0f / (float)(sd.renderedFramesCount + 1u); /* :316 */
-        const float iw = 1.0f - weight;
-        acc = mk3(o.x * iw + result.x * weight, o.y * iw + result.y * weight, o.z * iw + result.z * weight);
-    }
-    store_pixel(image, wire, wire_ch, wm, W, lx, ly, acc); /* :323 */
-}
 
 /* Shade one pixel (pathTracer.comp:290-323) with the given traversal stack. */
 template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A, int STAGE, class Stack>
@@ -429,8 +371,13 @@ struct MkLaunch {
     dev::SplitQueue q;
 };
 
-template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A, int STAGE>
-static hipError_t launch_mega(const MkLaunch& l)
+/* The tile order of a launch: tile_of_block's `scatter` and `order`, and where the launch records its tiles' times. */
+struct MkTiles {
+    uint32_t scatter;
+    const uint32_t* order;
+    uint32_t* cost;
+};
+static MkTiles mk_tiles(const MkLaunch& l, bool count)
 {
     const LaunchArgs& a = l.a;
     MkState& mk = l.mk;
@@ -452,16 +399,42 @@ static hipError_t launch_mega(const MkLaunch& l)
     }
     /* cost-ordered tiles (auto order, render launches): this render records every tile's time, and the renders after
      * a sort (launch_megakernel) take the tiles longest first */
-    const bool cost_order = !COUNT && a.mk_tile_order == 2 && mk.cost != nullptr;
+    const bool cost_order = !count && a.mk_tile_order == 2 && mk.cost != nullptr;
     const uint32_t* order = l.list ? l.list : (cost_order && mk.order_valid ? mk.order : nullptr);
+    return {scatter, order, cost_order ? mk.cost : nullptr};
+}
+
+template <bool COUNT, bool DIAG, int SK, bool PAIRS, bool SINGLE, bool REUSE, int PC, int A, int STAGE>
+static hipError_t launch_mega(const MkLaunch& l)
+{
+    const LaunchArgs& a = l.a;
+    const MkTiles t = mk_tiles(l, COUNT);
     typename dev::StageQueue<STAGE>::type qa; /* only a head has a queue argument */
     if constexpr (STAGE == dev::kStageHead) qa = l.q;
     hipLaunchKernelGGL((dev::pt_megakernel<COUNT, DIAG, SK, PAIRS, SINGLE, REUSE, PC, A, STAGE>),
-                       dim3(l.list ? l.grid : tiles), dim3(64), 0, l.stream, a.sd, a.materials, a.spheres, a.draws,
+                       dim3(l.list ? l.grid : l.tiles), dim3(64), 0, l.stream, a.sd, a.materials, a.spheres, a.draws,
                        a.tri_records, a.image, a.wire, a.wire_ch, a.W, a.H, RowMap{a.y0, a.row_shift, a.row_gap},
-                       a.wire_rows, a.rows, l.tilesX, tiles, scatter, order, cost_order ? mk.cost : nullptr, a.status,
-                       a.counters, PC != kPrimaryCacheNone ? static_cast<uint32_t*>(mk.prim_mem) : nullptr, qa);
+                       a.wire_rows, a.rows, l.tilesX, l.tiles, t.scatter, t.order, t.cost, a.status,
+                       a.counters, PC != kPrimaryCacheNone ? static_cast<uint32_t*>(l.mk.prim_mem) : nullptr, qa);
     return hipGetLastError();
+}
+
+/* The walk-only pair of a tiny tree's split render (pt_mk_tiny.hip), in the places of the general head and tail. */
+static hipError_t launch_tiny_pair(const MkLaunch& l, int pcmode)
+{
+    const LaunchArgs& a = l.a;
+    const MkTiles t = mk_tiles(l, false);
+    TinyHeadLaunch h;
+    h.grid = l.list ? l.grid : l.tiles;
+    h.tilesX = l.tilesX;
+    h.tiles = l.tiles;
+    h.scatter = t.scatter;
+    h.order = t.order;
+    h.cost = t.cost;
+    h.prim_cache = pcmode != kPrimaryCacheNone ? static_cast<uint32_t*>(l.mk.prim_mem) : nullptr;
+    hipError_t e = launch_tiny_head(a, pcmode, h, l.q, l.stream);
+    if (e == hipSuccess) e = launch_tiny_tail(a, l.q, l.stream);
+    return e;
 }
 
 /* the tail behind its head on the same stream: one wave per 64 entries of the queue's capacity */
@@ -698,6 +671,8 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
     const MkSelection sel = mk_variant_select(mode, stack_kind, a.pair_records, a.sd.drawCommandCount, a.sd.samples, pcmode,
                                               a.arith, cut != 0u);
     const bool split = sel.n == 2u;
+    /* a tiny tree's split render runs on the walk-only head and tail (mk_tiny_rule.h has the condition) */
+    const bool tiny = mk_tiny_kernels(mode, a.tiny_tree, split, sel.v[0].pairs, sel.v[0].single, sel.v[0].arith);
     if (split && lay.entries > mk.split_entries) { /* first: both counters of each pipe zero */
         mk.split_entries = 0;
         const size_t state_bytes = (size_t)lay.entries * kMkSplitEntryBytes;
@@ -720,7 +695,8 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
             l.q.cut = cut;
         }
         hipError_t le = hipSuccess; /* the whole kernel, or the head and then its tail */
-        for (uint32_t i = 0; i < sel.n && le == hipSuccess; i++) le = mk_dispatch(sel.v[i], l);
+        if (tiny) le = launch_tiny_pair(l, sel.v[0].pcache);
+        for (uint32_t i = 0; i < sel.n && !tiny && le == hipSuccess; i++) le = mk_dispatch(sel.v[i], l);
         if (le == hipSuccess && split) mk.split_parity[p] ^= 1u;
         return le;
     };
@@ -750,10 +726,7 @@ hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkSt
         e = launch(a, stream, nullptr, 0, 0u);
     }
     if (e == hipSuccess && split) mk.split_renders++;
-    /* the instances that hold the tiny-tree walk (pt_device.h kTinyWalk), on a draw whose table flag is set */
-    if (e == hipSuccess && mode == kModeRender && a.tiny_tree && split && sel.v[0].pairs && sel.v[0].single &&
-        sel.v[0].arith == WCPT_ARITH_EXACT)
-        mk.tiny_renders++;
+    if (e == hipSuccess && tiny) mk.tiny_renders++;
     if (e == hipSuccess && pcmode == kPrimaryCacheWrite) {
         mk.prim_key = *a.prim_key;
         mk.prim_valid = true;

@@ -102,7 +102,7 @@ __device__ __forceinline__ f3 TraceTail(PathState& ps, uint32_t& rng, const wcpt
     f3 L;
     float4 prim_rec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     for (;;) {
-        const Hit h = intersect<false, false, PAIRS, SINGLE, Stack, A, true>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
+        const Hit h = intersect<false, false, PAIRS, SINGLE, Stack, A>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
                                                                       overflow, false, prim_rec, false);
         if (path_shade<kShadeA<A>>(ps, h, rng, sd, mats, L, true)) return L;
     }
@@ -152,7 +152,7 @@ __device__ __forceinline__ f3 TraceRay(Ray ray, uint32_t& rng, const wcpt_scene_
                 }
             }
             if (done) return L;
-            h = intersect<COUNT, DIAG, PAIRS, SINGLE, Stack, A, STAGE == kStageHead>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
+            h = intersect<COUNT, DIAG, PAIRS, SINGLE, Stack, A>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
                                                                       overflow, false, prim_rec, false);
         }
     } else {
@@ -162,7 +162,7 @@ __device__ __forceinline__ f3 TraceRay(Ray ray, uint32_t& rng, const wcpt_scene_
     for (uint32_t seg = 0;; seg++) {
         const bool primary = seg == 0u;
         const bool reuse = REUSE && seg == 0u && reuse_primary;
-        const Hit h = intersect<COUNT, DIAG, PAIRS, SINGLE, Stack, A, STAGE == kStageHead>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
+        const Hit h = intersect<COUNT, DIAG, PAIRS, SINGLE, Stack, A>(ps.ray, sd, spheres, draws, tri_records, stk, cnt,
                                                                       overflow, primary, prim_rec, reuse);
         /* a traced primary segment: sample 0's. (The sample-reuse write build keeps the Intersect record in prim_rec
          * anyway and stores from the caller, after its sample loop: with the store here this toolchain's register

@@ -1,5 +1,5 @@
 /* pt_traversal.h -- Intersect (pathTracer.comp:135-211) for the megakernel: a draw's geometry, the leaf, interior, pop
- * and root steps, the tiny-tree walk, the traversal loop and the hit epilogue. Part of pt_device.h. */
+ * and root steps, the traversal loop and the hit epilogue. Part of pt_device.h. (The walk of a tiny tree: pt_tiny.h.) */
 #ifndef WCPT_PT_TRAVERSAL_H
 #define WCPT_PT_TRAVERSAL_H
 
@@ -338,118 +338,6 @@ __device__ __forceinline__ bool root_step(const Ray& ray, const DrawGeom& g, flo
     return true;
 }
 
-/* ---- tiny trees (mk_tiny_rule.h, table flag kTriFlagTinyTree): a root leaf, or a root over two leaves --------------
- * The nodes are the same for every lane, so the wave reads them with scalar loads and the leaves' record ranges are SALU
- * values: no stack, no mode loop, no per-lane leaf cursor, no empty pop. What stays per lane is the reference's own
- * arithmetic and its decisions -- the three slab tests, root_step's cull (root_survives), interior_step's order and its
- * two box passes (child_pair), the pop's cull of the far child against the rec.t the near leaf left -- through the same
- * definitions, NaN behaviour included. A leaf is run by the whole wave under a wave-uniform branch (some lane visits
- * it), and a lane that the reference would not have brought there takes nothing (`visit`): there is no wave-uniform loop
- * under divergent control.
- * The walk is the draw's whole traversal: the traversal loop is not entered behind it (intersect branches once).
- * rec.t stays in its integer form (take_bits) and the winner a record tag across both leaves, decoded once. */
-/* The leaf's triangles [k0, kend), both wave-uniform, as one scalar loop over the pair records that hold them. Every
- * pair is tested the same way; a pair of which the leaf owns only one slot (it starts in slot 1, or ends in slot 0)
- * takes only that slot: whether a slot is the leaf's is a SALU condition on the takes. Only visiting lanes take.
- * Applied in index order, strict <: pair_take_bits. (Two leaves that share a pair test it once each; DESIGN.md section
- * 3 has why.) */
-template <bool PRIM, int A>
-__device__ __forceinline__ void tiny_leaf(const Ray& ray, const WCPT_GLOBAL char* pbase, uint32_t k0, uint32_t kend,
-                                          bool visit, uint32_t& rb, uint32_t& tag)
-{
-    constexpr uint32_t kBytes = PRIM ? kPrimPairRecordBytes : kPairRecordBytes;
-    const uint32_t oEnd = ((kend + 1u) >> 1) * kBytes;
-    uint32_t k = k0 & ~1u; /* the first triangle of the pair at o */
-    for (uint32_t o = (k0 >> 1) * kBytes; o < oEnd; o += kBytes, k += 2u) {
-        const bool own0 = k >= k0, own1 = k + 1u < kend; /* wave-uniform */
-        PairHit ph;
-        if constexpr (PRIM) {
-            const TriPairP p = load_pairP_const(pbase, o);
-            v2f px, py, pz;
-            const v2f det = pairP_det<A>(ray, p, px, py, pz);
-            /* no visiting lane can take either triangle: pair_leaf's sign pre-reject */
-            if (__builtin_amdgcn_ballot_w64(visit && pairP_may_take(p, det)) == 0ull) continue;
-            ph = pairP_finish<A>(ray, p, px, py, pz, det);
-        } else {
-            ph = rayTrianglePair<A>(ray, load_pair_const(pbase, o));
-        }
-        ph.hit0 = ph.hit0 && visit && own0;
-        ph.hit1 = ph.hit1 && visit && own1;
-        pair_take_bits(ph, o, rb, tag);
-    }
-}
-/* One lane's side of a tiny tree: whether it is inside the root's box (root_survives), and under an interior root the
- * child-pair decision (child_pair; all false and unread under a root leaf). */
-struct TinyLane { bool in; ChildPair c; };
-/* The leaves of the walk. A root leaf (n == 1) is visited by the lanes inside its box. Under an interior root the leaves
- * run in up to four turns: left then right for the lanes that pop the left child first, right then left for the others.
- * In a turn a lane of that group visits the leaf iff it passed the leaf's box and the box's entry distance is not beyond
- * rec.t as it stands when the turn comes (:162; for a lane's near child that is interior_step's `!(nearT0 > rt)`, for
- * its far child the pop's cull). A turn no lane takes is skipped by one ballot, so a wave whose lanes agree on the order
- * -- almost every wave where the two boxes coincide -- runs two. The groups are disjoint, so each lane sees its two
- * leaves in the reference's order. */
-template <bool PRIM, int A>
-__device__ __forceinline__ void tiny_leaves(const Ray& ray, gtri_ptr recs, uint32_t n, uint32_t firstL, uint32_t countL,
-                                            uint32_t firstR, uint32_t countR, const TinyLane& t, float& rt,
-                                            uint32_t& prim)
-{
-    constexpr uint32_t kBytes = PRIM ? kPrimPairRecordBytes : kPairRecordBytes;
-    const WCPT_GLOBAL char* pbase = reinterpret_cast<const WCPT_GLOBAL char*>(recs);
-    uint32_t rb = take_bits(rt), tag = kNoTag;
-#pragma clang loop unroll(disable)
-    for (uint32_t i = 0; i < n; i++) {
-        /* turn i: group i >> 1 (0: left-first lanes), position i & 1 (0: the lane's near child); the right leaf iff
-         * group and position differ */
-        const bool right = ((i >> 1) ^ (i & 1u)) != 0u;
-        bool visit = t.in;
-        if (n != 1u)
-            visit = t.in && (t.c.leftFirst == (i < 2u)) && (right ? t.c.passR : t.c.passL) &&
-                    !((right ? t.c.r0 : t.c.l0) > __uint_as_float(rb + 1u));
-        if (__builtin_amdgcn_ballot_w64(visit) == 0ull) continue;
-        /* mk_tiny_rule.h: the leaf starts on a triangle boundary, inside the records */
-        const uint32_t k0 = __builtin_amdgcn_readfirstlane((right ? firstR : firstL) / 3u);
-        const uint32_t kend = k0 + __builtin_amdgcn_readfirstlane(((right ? countR : countL) + 2u) / 3u);
-        tiny_leaf<PRIM, A>(ray, pbase, k0, kend, visit, rb, tag);
-    }
-    if (tag != kNoTag) prim = 3u * (2u * (tag / kBytes) + (tag & 1u));
-    rt = __uint_as_float(rb + 1u);
-}
-/* The instances that hold the walk: the two launches of a split render (SPLIT: head and tail, mk_split_rule.h -- the
- * renders the automatic rule splits are the large one-sample frames of scenes of at most 64 triangles, which is where
- * tiny trees are) in exact arithmetic on pair records (with one draw command: intersect's SINGLE branch). The whole
- * kernels, which every larger mesh runs, and the fast-arithmetic builds keep the loop alone and with it the
- * instruction stream they had: with the walk compiled beside the loop the reference's scene measured 0.5-1.3 % slower
- * on its whole kernel, and the fast builds lost a wave per SIMD. */
-template <bool COUNT, bool DIAG, bool PAIRS, int A, bool SPLIT>
-constexpr bool kTinyWalk = SPLIT && PAIRS && !COUNT && !DIAG && A == kArithExact;
-/* The draw's whole traversal for a tiny tree. */
-template <int A>
-__device__ __forceinline__ void tiny_walk(const Ray& ray, const DrawGeom& g, bool primary, float& rt, uint32_t& prim,
-                                          Counters& cnt)
-{
-    const NodeV root = load_node_const(g.bvh, 0);
-    TinyLane t;
-    t.in = root_survives(ray, root, rt);
-    t.c = ChildPair{false, false, false, 0.0f, 0.0f};
-    uint32_t n = 1u, firstL = root.b.z, countL = root.b.w, firstR = 0u, countR = 0u; /* a root leaf: the "left" one */
-    if (root.b.w == 0u) { /* wave-uniform: interior_step on the two leaves */
-        const NodeV L = load_node_const(g.bvh, root.b.z);
-        const NodeV R = load_node_const(g.bvh, root.b.z + 1u);
-        t.c = child_pair(ray, L, R);
-        n = 4u;
-        firstL = L.b.z;
-        countL = L.b.w;
-        firstR = R.b.z;
-        countR = R.b.w;
-    }
-    phase_mark(cnt, 2);
-    if (primary && g.ptris != nullptr)
-        tiny_leaves<true, A>(ray, g.ptris, n, firstL, countL, firstR, countR, t, rt, prim);
-    else
-        tiny_leaves<false, A>(ray, g.tris, n, firstL, countL, firstR, countR, t, rt, prim);
-    phase_mark(cnt, 3);
-}
-
 /* pathTracer.comp:135-211. PAIRS: leaf tests on pair records (else single records).
  *
  * SINGLE (drawCommandCount == 1, the reference's own case, PathTracingRenderer.jai:251): the draw's geometry is
@@ -522,7 +410,7 @@ __device__ __forceinline__ Hit prim_entry_hit(const PrimEntry& e, f3 origin, f3&
     h.p = axpy_a<A>(origin, dir, h.t); /* :205, resolve_hit's */
     return h;
 }
-template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, int A = kArithExact, bool SPLIT = false>
+template <bool COUNT, bool DIAG, bool PAIRS, bool SINGLE, class Stack, int A = kArithExact>
 __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& sd, const wcpt_sphere* __restrict__ spheres,
                                          const wcpt_draw_command* __restrict__ draws,
                                          const uint64_t* __restrict__ tri_records, Stack& stk,
@@ -574,14 +462,8 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
              * leaf tests it in the same iteration */
             enum : uint32_t { kInterior = 0, kLeaf = 1, kPop = 2, kDone = 3 };
             uint32_t mode = kDone;
-            /* a tiny tree (kTinyWalk: the split render's exact builds on pair records; the counting builds keep the reference walk and its
-             * counters) is walked instead of this loop: one wave-uniform branch around the whole traversal */
-            bool tiny = false;
-            if constexpr (kTinyWalk<COUNT, DIAG, PAIRS, A, SPLIT>)
-                tiny = sd.drawCommandCount != 0u && (tri_records[kTriWordFlags] & kTriFlagTinyTree) != 0u;
-            if (tiny) {
-                if constexpr (kTinyWalk<COUNT, DIAG, PAIRS, A, SPLIT>) tiny_walk<A>(ray, g, primary, rt, prim, cnt);
-            } else if (sd.drawCommandCount != 0u && root_step<COUNT>(ray, g, rt, curLeft, curCount, cnt, rf)) {
+            /* (a tiny tree's render -- mk_tiny_rule.h mk_tiny_kernels -- does not come here: pt_mk_tiny.hip) */
+            if (sd.drawCommandCount != 0u && root_step<COUNT>(ray, g, rt, curLeft, curCount, cnt, rf)) {
                 stk.reset();
                 mode = curCount > 0 ? kLeaf : kInterior;
             }
