@@ -1,6 +1,6 @@
 """Frame overlap (WCPT_OPTION_FRAME_OVERLAP) on the GPU: consecutive megakernel renders split the cost-ordered tiles
 between two pipes (pt_kernels.hip launch_megakernel) and the wavefront kernel's pipelines skip their per-frame join
-(pt_wavefront.hip launch_wavefront), so each pipe runs on into its next frame. Each pixel stays with one pipe, and
+(wf_plan.h wf_frame_continues, applied by pt_wavefront.hip launch_wavefront), so each pipe runs on into its next frame. Each pixel stays with one pipe, and
 every other entry point joins the pipes into the context's stream first, so the results must be the plain stream's bit
 for bit:
 

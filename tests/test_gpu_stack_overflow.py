@@ -13,8 +13,8 @@ The refused subtree is simply not visited, the kernels atomicOr the context's st
 wcpt_sync / wcpt_readback / wcpt_render_counters reports WCPT_ERROR_STACK_OVERFLOW once and clears the word
 (wcpt_runtime.hip read_status).
 
-Which instance a one-draw hand-made chain selects (pt_wavefront.hip wf_geo, wf_trace_geo, wf_dispatch, launch_wavefront):
-uploaded through wcpt_buffer_upload it gets the fast layout (packed refs, 24-bit offsets, 3-index leaves on records, a
+Which instance a one-draw hand-made chain selects (wf_plan.h wf_variant_select, wf_frame_plan, wf_pipe_geo and
+wf_pipe_variant, which tests/test_wf_plan.py evaluates on the CPU; pt_wavefront.hip wf_dispatch launches it): uploaded through wcpt_buffer_upload it gets the fast layout (packed refs, 24-bit offsets, 3-index leaves on records, a
 known node count), so at WCPT_OPTION_WF_STACK 10 a 48x32 one-sample frame takes the path-persistent trace
 wf_trace<false, false, 3, 10, true> (1536 paths fit the resident lanes), with WCPT_OPTION_WF_PERSIST 0 the one-round
 trace <.., 3, 10> (WCPT_OPTION_WF_FETCH 1 or auto at this size) or the two-round <.., 2, 10> (WF_FETCH 0); with

@@ -6,8 +6,8 @@ Morton code of the origin in draw 0's root box) and traced in that order. The or
 enters a result, so a sorted frame and its counters are the oracle's bit for bit; a slot that the order names twice or
 not at all loses or doubles a path and shows in both.
 
-LDS stack depth: WCPT_OPTION_WF_STACK = 16 / 24 select wf_trace<false, false, 1, 16> / <..., 1, 24> (wf_geo: a depth
-other than 10 leaves the fast layout's GEO 2 / 3), each with its own LDS size, launch bounds and LDS-to-scratch boundary
+LDS stack depth: WCPT_OPTION_WF_STACK = 16 / 24 select wf_trace<false, false, 1, 16> / <..., 1, 24> (wf_plan.h wf_variant_select: a
+depth other than 10 leaves the fast layout's GEO 2 / 3), each with its own LDS size, launch bounds and LDS-to-scratch boundary
 (LdsStack<LDSN, 48 - LDSN>). The 40-level chain of tests/deep_tree.py holds 40 far children at its bottom, so it crosses
 that boundary at entry 10, 16 and 24. At depth 10 a one-draw frame on the fast layout takes what production takes there:
 GEO 2 / 3, or on frames this small the path-persistent trace; tests/test_gpu_stack_overflow.py selects each instance.
@@ -160,8 +160,8 @@ def test_sort_scratch_regrows():
 @pytest.mark.parametrize("extra", [{"wf_pipes": 3}, {"wf_persist": 1}, {"wf_pipes": 3, "wf_persist": 1}, {"wf_fetch": 0},
                                    {"wf_fetch": 1}], ids=lambda e: "-".join(f"{k}{v}" for k, v in e.items()))
 def test_sort_with_pipelines_and_persist(gpu_ctx, extra):
-    """With the sort on, launch_wavefront runs one pipeline whatever WCPT_OPTION_WF_PIPES says (one sort scratch) and
-    never the path-persistent trace (persist_ok needs !sort_rays); either fetch-round instance reads the order. The
+    """With the sort on, wf_frame_plan (wf_plan.h) gives one pipeline whatever WCPT_OPTION_WF_PIPES says (one sort scratch)
+    and never the path-persistent trace (wf_persist_eligible needs an unsorted render); either fetch-round instance reads the order. The
     frame is the oracle's."""
     with options(gpu_ctx, sort_rays=1, **extra):
         _check(gpu_ctx, ("cornell", 200, 150, 3, 1))

@@ -12,6 +12,7 @@
 #include "mk_variant.h"
 #include "primary_cache_key.h"
 #include "row_map.h"
+#include "wf_plan.h"
 
 namespace wcpt {
 
@@ -106,8 +107,7 @@ struct WfState {
     void* sort_temp = nullptr;
     size_t sort_temp_bytes = 0;
     int cus = 0;                   /* compute units of the context's device (0 = not yet queried)          */
-    int trace_bpc[3][3][3] = {};   /* trace-kernel blocks per CU by (mode, geometry variant, LDS stack)      */
-    int persist_bpc = 0;           /* the path-persistent trace's blocks per CU                             */
+    int bpc[kWfVariantCodes] = {}; /* wf_trace blocks per CU by wf_variant_code (wf_plan.h); 0 = not yet queried */
     /* queue counters: two sets of {count q0, count q1, trace head, -}; a frame uses set `parity` and its ray generation
      * zeroes the other set for the next frame (pt_wavefront.hip wf_init); `ctr_fresh` until the first zeroing */
     uint32_t parity = 0;
@@ -117,8 +117,7 @@ struct WfState {
 /* Concurrent wavefront pipelines (WCPT_OPTION_WF_PIPES): pipeline j of K owns the 8x8 tiles t with t % K == j and
  * runs its own init / trace / shade sequence on its own stream (pipeline 0 on the context's stream), so the tail of
  * one pipeline's trace (a few slow rays on an otherwise idle chip) overlaps the bulk of another's. Paths never
- * interact, so the image and the counters are those of one pipeline. */
-constexpr int kWfMaxPipes = 4;
+ * interact, so the image and the counters are those of one pipeline. kWfMaxPipes: wf_plan.h. */
 struct WfPipes {
     WfState pipe[kWfMaxPipes];
     float4* result = nullptr;            /* by pixel: sum of sample radiance .xyz (all pipelines) */

@@ -39,7 +39,7 @@ namespace dev {
 #define WCPT_TRACE_CHUNK 64
 #endif
 constexpr uint32_t kTraceChunk = WCPT_TRACE_CHUNK;
-constexpr int kShadeBlock = 256;
+constexpr int kShadeBlock = (int)kWfShadeBlock; /* wf_plan.h sizes the grids by it */
 
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
@@ -101,16 +101,13 @@ __device__ __forceinline__ uint32_t block_append(uint32_t* counter, bool pred, u
 #ifndef WCPT_WF_TAIL_WINDOW
 #define WCPT_WF_TAIL_WINDOW 16 /* rays per wave of the grid: claims for idle lanes only in the queue's last window */
 #endif
-/* Path-persistent trace (PERSIST instances, launch_wavefront): one launch runs every segment of its paths. A lane whose
+/* Path-persistent trace (PERSIST instances; wf_plan.h wf_frame_plan): one launch runs every segment of its paths. A lane whose
  * ray is done shades it in place (resolve_hit, path_shade, the next segment's sphere loop, or the pixel's store) and
  * goes on with the path's next segment, so no path waits for the slowest ray of its bounce; the wave shades once
  * `refill` of its lanes wait, or when none is tracing. Used where a pipeline's queue is short (row blocks), for one
  * sample per pixel. */
 #ifndef WCPT_WF_PERSIST_WAVES
 #define WCPT_WF_PERSIST_WAVES 4
-#endif
-#ifndef WCPT_WF_PERSIST_GEO
-#define WCPT_WF_PERSIST_GEO 3 /* the persistent trace's fetch rounds: 3 one per iteration, 2 two */
 #endif
 #ifndef WCPT_WF_GEO2_WAVES
 #define WCPT_WF_GEO2_WAVES 8 /* occupancy floor of the fast-layout trace (waves per SIMD) */
@@ -849,90 +846,60 @@ __global__ __launch_bounds__(256) void wf_sort_keys(WfBuffers b, uint32_t P, con
     }
 }
 
-template <bool COUNT, bool DIAG, int GEO, int LDSN>
-static void wf_iteration(const LaunchArgs& a, const WfBuffers& b, uint32_t trace_grid, uint32_t shade_grid,
-                         hipStream_t stream)
+/* The dispatcher: a runtime WfVariant becomes wf_trace's template arguments. Every field combination has a number
+ * (wf_variant_code), each number a function, and only the combinations wf_variant_built admits have a kernel behind
+ * theirs -- so wf_plan.h is the list of the wf_trace instances this file compiles. The function launches its instance
+ * (`l`), or without a launch reports the instance's blocks per CU (`bpc`). */
+struct WfTraceLaunch {
+    const LaunchArgs& a;
+    const WfBuffers& b;
+    uint32_t grid;
+    hipStream_t stream;
+};
+template <uint32_t CODE>
+static hipError_t wf_instance(const WfTraceLaunch* l, int* bpc)
 {
-    hipLaunchKernelGGL((dev::wf_trace<COUNT, DIAG, GEO, LDSN>), dim3(trace_grid), dim3(64), 0, stream, a.sd, a.draws,
-                       a.tri_records, b, a.status, a.counters, a.wf_refill, a.materials, a.spheres, a.image, a.W, a.H);
-    hipLaunchKernelGGL(dev::wf_shade<COUNT>, dim3(shade_grid), dim3(dev::kShadeBlock), 0, stream, a.sd, a.materials,
-                       a.spheres, a.draws, a.tri_records, b, a.image, a.W, a.H, RowMap{a.y0, a.row_shift, a.row_gap}, a.counters);
+    constexpr WfVariant v = wf_variant_decode(CODE);
+    if constexpr (!wf_variant_built(v)) return hipErrorInvalidValue;
+    else {
+        const auto kernel = dev::wf_trace<v.count, v.diag, v.geo, v.ldsn, v.persist>;
+        if (!l) return hipOccupancyMaxActiveBlocksPerMultiprocessor(bpc, kernel, 64, 0);
+        const LaunchArgs& a = l->a;
+        hipLaunchKernelGGL(kernel, dim3(l->grid), dim3(64), 0, l->stream, a.sd, a.draws, a.tri_records, l->b, a.status,
+                           a.counters, v.persist ? a.wf_refill_persist : a.wf_refill, a.materials, a.spheres, a.image, a.W,
+                           a.H);
+        return hipGetLastError();
+    }
 }
+template <size_t... CODE>
+static hipError_t wf_dispatch(const WfVariant& v, const WfTraceLaunch* l, int* bpc, std::index_sequence<CODE...>)
+{
+    static constexpr hipError_t (*table[])(const WfTraceLaunch*, int*) = {&wf_instance<(uint32_t)CODE>...};
+    return wf_variant_built(v) ? table[wf_variant_code(v)](l, bpc) : hipErrorInvalidValue;
+}
+static hipError_t wf_dispatch(const WfVariant& v, const WfTraceLaunch* l, int* bpc)
+{
+    return wf_dispatch(v, l, bpc, std::make_index_sequence<kWfVariantCodes>{});
+}
+constexpr uint32_t wf_built_count()
+{
+    uint32_t n = 0;
+    for (uint32_t c = 0; c < kWfVariantCodes; c++) n += wf_variant_built(wf_variant_decode(c)) ? 1u : 0u;
+    return n;
+}
+static_assert(wf_built_count() == 12, "the code object holds twelve wf_trace instances (wf_plan.h)");
 
-template <bool COUNT, bool DIAG, int GEO, int LDSN>
-static hipError_t trace_blocks_per_cu(int& bpc)
+/* Blocks per CU of instance v, queried once per context. */
+static hipError_t wf_occupancy(WfState& s0, const WfVariant& v, int& bpc)
 {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, dev::wf_trace<COUNT, DIAG, GEO, LDSN>, 64, 0);
-}
-
-/* One (mode, single-draw, LDS depth) instantiation: occupancy query or one trace+shade iteration. */
-template <bool COUNT, bool DIAG, int GEO, int LDSN>
-static hipError_t wf_variant(bool query, int& bpc, const LaunchArgs& a, const WfBuffers& b, uint32_t trace_grid,
-                             uint32_t shade_grid, hipStream_t stream)
-{
-    if (query) return trace_blocks_per_cu<COUNT, DIAG, GEO, LDSN>(bpc);
-    wf_iteration<COUNT, DIAG, GEO, LDSN>(a, b, trace_grid, shade_grid, stream);
-    return hipGetLastError();
-}
-
-/* The path-persistent trace (PERSIST): one launch for every segment of the pipeline's paths; GEO 2 or 3. */
-template <int GEO>
-static hipError_t wf_persist_variant(bool query, int& bpc, const LaunchArgs& a, const WfBuffers& b, uint32_t grid,
-                                     hipStream_t stream)
-{
-    if (query)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, dev::wf_trace<false, false, GEO, 10, true>, 64, 0);
-    hipLaunchKernelGGL((dev::wf_trace<false, false, GEO, 10, true>), dim3(grid), dim3(64), 0, stream, a.sd, a.draws,
-                       a.tri_records, b, a.status, a.counters, a.wf_refill_persist, a.materials, a.spheres, a.image, a.W,
-                       a.H);
-    return hipGetLastError();
-}
-static hipError_t wf_persist_dispatch(int geo, bool query, int& bpc, const LaunchArgs& a, const WfBuffers& b,
-                                      uint32_t grid, hipStream_t stream)
-{
-    return geo == 3 ? wf_persist_variant<3>(query, bpc, a, b, grid, stream)
-                    : wf_persist_variant<2>(query, bpc, a, b, grid, stream);
-}
-
-static hipError_t wf_dispatch(int mode, int geo, int ldsn, bool query, int& bpc, const LaunchArgs& a,
-                              const WfBuffers& b, uint32_t tg, uint32_t sg, hipStream_t st)
-{
-    const bool single = geo >= 1;
-    if (mode == kModeCount) return single ? wf_variant<true, false, 1, 10>(query, bpc, a, b, tg, sg, st)
-                                          : wf_variant<true, false, 0, 10>(query, bpc, a, b, tg, sg, st);
-    if (mode == kModeDiag) return single ? wf_variant<true, true, 1, 10>(query, bpc, a, b, tg, sg, st)
-                                         : wf_variant<true, true, 0, 10>(query, bpc, a, b, tg, sg, st);
-    if (!single) return wf_variant<false, false, 0, 10>(query, bpc, a, b, tg, sg, st);
-    if (geo == 2) return wf_variant<false, false, 2, 10>(query, bpc, a, b, tg, sg, st);
-    if (geo == 3) return wf_variant<false, false, 3, 10>(query, bpc, a, b, tg, sg, st);
-    if (ldsn == 16) return wf_variant<false, false, 1, 16>(query, bpc, a, b, tg, sg, st);
-    if (ldsn == 24) return wf_variant<false, false, 1, 24>(query, bpc, a, b, tg, sg, st);
-    return wf_variant<false, false, 1, 10>(query, bpc, a, b, tg, sg, st);
-}
-
-/* The trace instantiation for this launch: 0 any draws, 1 one draw, 2 one draw on the fast layout (render build, the
- * default LDS stack; LaunchArgs::wf_fast). */
-static int wf_geo(const LaunchArgs& a, int mode, int ldsn)
-{
-    if (a.sd.drawCommandCount != 1) return 0;
-    return (a.wf_fast && mode == kModeRender && ldsn == 10) ? 2 : 1;
-}
-
-/* One fetch round per trace iteration (GEO 3) or two (GEO 2: a lane that descends into a leaf tests its first
- * triangle in the same iteration, after the interior lanes' fetch). One round overlaps the interior and leaf lanes'
- * fetches, which pays where fetch latency is exposed -- few queued rays per resident lane, so much of the launch is
- * its tail -- and costs an iteration per leaf descent, which loses where the chip is issue-bound on a long queue.
- * Measured (profiles/r05_fetch_once_ab.log): c3 (4.0 rays per lane per pipeline) 4.52 against 4.66 ms; c4 (15.8)
- * 203.6 against 199.6 ms. WCPT_OPTION_WF_FETCH: -1 (default) by that ratio, 0 two rounds, 1 one round. */
-#ifndef WCPT_WF_FETCH_ONCE_RATIO
-#define WCPT_WF_FETCH_ONCE_RATIO 8
-#endif
-static int wf_trace_geo(const LaunchArgs& a, int mode, int ldsn, uint32_t P, uint32_t trace_grid)
-{
-    const int geo = wf_geo(a, mode, ldsn);
-    if (geo != 2 || a.wf_fetch == 0) return geo;
-    if (a.wf_fetch > 0) return 3;
-    return (uint64_t)P <= (uint64_t)WCPT_WF_FETCH_ONCE_RATIO * 64ull * trace_grid ? 3 : 2;
+    int& cached = s0.bpc[wf_variant_code(v)];
+    if (cached == 0) {
+        hipError_t e = wf_dispatch(v, nullptr, &cached);
+        if (e != hipSuccess) return e;
+        if (cached < 1) cached = 1;
+    }
+    bpc = cached;
+    return hipSuccess;
 }
 
 static hipError_t sort_queue(const LaunchArgs& a, WfState& s, const WfBuffers& b, uint32_t P, int cus,
@@ -950,20 +917,28 @@ static hipError_t sort_queue(const LaunchArgs& a, WfState& s, const WfBuffers& b
                                               s.sort_order, (int)P, 0, 32, stream);
 }
 
-/* One pipeline: init (pipe_begin) + samples*(maxBounce+1) trace/shade iterations (pipe_iterate) over the tiles t with
- * t % npipes == pipe. */
-static hipError_t pipe_begin(const LaunchArgs& a, int mode, WfState& s, const WfState& s0, float4* result, float4* prim_hit,
-                             uint32_t pipe, uint32_t npipes, int cus, hipStream_t stream, WfBuffers& b)
+template <bool COUNT>
+static void launch_init(const LaunchArgs& a, const WfBuffers& b, const WfFramePlan& plan, uint32_t j, uint32_t* zero_next,
+                        hipStream_t stream)
 {
-    const uint32_t tilesX = (a.W + 7u) / 8u;
-    const uint32_t tiles = tilesX * ((a.rows + 7u) / 8u);
-    if (pipe >= tiles) return hipSuccess;
-    const uint32_t total = ((tiles - pipe + npipes - 1u) / npipes) * 64u;
-    /* live paths of this pipeline <= its pixels: the slot arrays are sized by its share of the tiles, not the frame */
-    const uint32_t P = min(total, a.W * a.rows);
-    hipError_t e = wf_reserve(s, P);
+    hipLaunchKernelGGL(dev::wf_init<COUNT>, dim3(plan.pipe[j].init_grid), dim3(dev::kShadeBlock), 0, stream, a.sd, a.spheres,
+                       b, a.image, a.W, a.H, RowMap{a.y0, a.row_shift, a.row_gap}, a.rows, (a.W + 7u) / 8u,
+                       plan.pipe[j].total, j, plan.K, a.counters, zero_next);
+}
+template <bool COUNT>
+static void launch_shade(const LaunchArgs& a, const WfBuffers& b, const WfFramePlan& plan, hipStream_t stream)
+{
+    hipLaunchKernelGGL(dev::wf_shade<COUNT>, dim3(plan.shade_grid), dim3(dev::kShadeBlock), 0, stream, a.sd, a.materials,
+                       a.spheres, a.draws, a.tri_records, b, a.image, a.W, a.H, RowMap{a.y0, a.row_shift, a.row_gap}, a.counters);
+}
+
+/* Pipeline j of the plan: init (pipe_begin) + its trace/shade iterations, or its one persistent launch (pipe_iterate),
+ * over the tiles t with t % K == j. */
+static hipError_t pipe_begin(const LaunchArgs& a, const WfVariant& base, const WfFramePlan& plan, uint32_t j, WfState& s,
+                             const WfState& s0, float4* result, float4* prim_hit, hipStream_t stream, WfBuffers& b)
+{
+    hipError_t e = wf_reserve(s, plan.pipe[j].paths);
     if (e != hipSuccess) return e;
-    const bool count = mode != kModeRender;
     /* The queue counters must start at zero. The pipeline alternates between two counter sets, and each frame's
      * wf_init zeroes the set the next frame uses -- the frames of one pipeline run in order on its stream (and a
      * render's pipelines join before the next render forks), so the previous frame, the only other user of that set,
@@ -986,7 +961,7 @@ static hipError_t pipe_begin(const LaunchArgs& a, int mode, WfState& s, const Wf
     b.order = nullptr;
     b.head = ctr + 2;
     b.diag = s0.diag;
-    if (mode == kModeDiag) {
+    if (base.diag) {
         e = hipMemsetAsync(s0.diag, 0, dev::kDiagTimers * sizeof(unsigned long long), stream);
         if (e != hipSuccess) return e;
     }
@@ -995,48 +970,32 @@ static hipError_t pipe_begin(const LaunchArgs& a, int mode, WfState& s, const Wf
     b.wire_rows = a.wire_rows;
     b.count_in = ctr + 0;
     b.count_out = ctr + 1;
-    const uint32_t init_grid = min((total + dev::kShadeBlock - 1) / dev::kShadeBlock, (uint32_t)cus * 16u);
-    if (count)
-        hipLaunchKernelGGL(dev::wf_init<true>, dim3(init_grid), dim3(dev::kShadeBlock), 0, stream, a.sd, a.spheres, b, a.image,
-                           a.W, a.H, RowMap{a.y0, a.row_shift, a.row_gap}, a.rows, tilesX, total, pipe, npipes, a.counters,
-                           zero_next);
-    else
-        hipLaunchKernelGGL(dev::wf_init<false>, dim3(init_grid), dim3(dev::kShadeBlock), 0, stream, a.sd, a.spheres, b, a.image,
-                           a.W, a.H, RowMap{a.y0, a.row_shift, a.row_gap}, a.rows, tilesX, total, pipe, npipes, a.counters,
-                           zero_next);
+    if (base.count) launch_init<true>(a, b, plan, j, zero_next, stream);
+    else launch_init<false>(a, b, plan, j, zero_next, stream);
     return hipGetLastError();
 }
 
-static hipError_t pipe_iterate(const LaunchArgs& a, int mode, WfState& s, uint32_t pipe, uint32_t npipes,
-                               bool sort_rays, int ldsn, int cus, uint32_t trace_grid, uint32_t shade_grid,
-                               uint32_t persist_grid, hipStream_t stream, WfBuffers b)
+static hipError_t pipe_iterate(const LaunchArgs& a, const WfVariant& base, const WfFramePlan& plan, uint32_t j, WfState& s,
+                               bool sort_rays, int cus, hipStream_t stream, WfBuffers b)
 {
-    const uint32_t tilesX = (a.W + 7u) / 8u;
-    const uint32_t tiles = tilesX * ((a.rows + 7u) / 8u);
-    if (pipe >= tiles) return hipSuccess;
-    const uint32_t P = min(((tiles - pipe + npipes - 1u) / npipes) * 64u, a.W * a.rows); /* as pipe_begin */
-    /* one draw: the reference's case (PathTracingRenderer.jai:251) */
-    const int geo = wf_trace_geo(a, mode, ldsn, P, trace_grid);
-    hipError_t e = hipSuccess;
-    if (persist_grid) { /* every segment in one launch (launch_wavefront) */
-        int unused = 0;
-        return wf_persist_dispatch(WCPT_WF_PERSIST_GEO, false, unused, a, b, persist_grid, stream);
+    const WfVariant v = wf_pipe_variant(plan, base, j);
+    if (plan.persist) { /* every segment in one launch */
+        const WfTraceLaunch l = {a, b, plan.persist_grid, stream};
+        return wf_dispatch(v, &l, nullptr);
     }
-    /* each iteration advances every live path by one traced segment; a path needs <= samples*(maxBounce+1), or
-     * with the primary records reused (wf_shade) maxBounce+1 for sample 0 and maxBounce for each later sample */
-    uint64_t iters = (uint64_t)a.sd.samples * ((uint64_t)a.sd.maxBounceCount + 1ull);
-    if (mode == kModeRender && a.sd.samples > 1u)
-        iters = (uint64_t)a.sd.maxBounceCount + 1ull + (uint64_t)(a.sd.samples - 1u) * a.sd.maxBounceCount;
-    if (iters > (1ull << 20)) iters = 1ull << 20; /* bounded; WCPT documents the cap */
-    for (uint64_t it = 0; it < iters; it++) {
+    for (uint32_t it = 0; it < plan.pipe[j].iters; it++) {
         b.order = nullptr;
         if (sort_rays && it > 0) { /* bounce rays; the primary queue is already in 8x8-tile order */
-            e = sort_queue(a, s, b, P, cus, stream);
+            hipError_t e = sort_queue(a, s, b, plan.pipe[j].paths, cus, stream);
             if (e != hipSuccess) return e;
             b.order = s.sort_order;
         }
-        int unused = 0;
-        e = wf_dispatch(mode, geo, ldsn, false, unused, a, b, trace_grid, shade_grid, stream);
+        const WfTraceLaunch l = {a, b, plan.trace_grid, stream};
+        hipError_t e = wf_dispatch(v, &l, nullptr);
+        if (e != hipSuccess) return e;
+        if (base.count) launch_shade<true>(a, b, plan, stream);
+        else launch_shade<false>(a, b, plan, stream);
+        e = hipGetLastError();
         if (e != hipSuccess) return e;
         std::swap(b.in, b.out);
         std::swap(b.count_in, b.count_out);
@@ -1057,98 +1016,41 @@ hipError_t wf_join(WfPipes& w, hipStream_t stream)
     return first;
 }
 
+/* Every decision about the frame is wf_plan.h's (wf_variant_select, wf_frame_plan, wf_frame_continues); this function
+ * asks the device what the plan needs and carries it out. */
 hipError_t launch_wavefront(const LaunchArgs& a, int mode, WfPipes& w, int pipes, bool sort_rays, int lds_stack,
                             hipStream_t stream, int overlap)
 {
-    const uint32_t tilesX = (a.W + 7u) / 8u;
-    const uint32_t tilesY = (a.rows + 7u) / 8u;
-    const uint64_t total64 = (uint64_t)tilesX * tilesY * 64ull;
-    if (total64 == 0) return hipSuccess;
-    if (total64 > 0xFFFFFFC0ull || (uint64_t)a.W * a.rows > 0xFFFFFFFFull) return hipErrorInvalidValue;
     WfState& s0 = w.pipe[0];
     int cus = 0;
     hipError_t e = cu_count(s0, cus);
     if (e != hipSuccess) return e;
-    const int ldsn = (lds_stack == 16 || lds_stack == 24) ? lds_stack : 10;
-    const int geo = wf_geo(a, mode, ldsn); /* GEO 3 (wf_trace_geo) runs at GEO 2's occupancy: both 8 waves/SIMD */
-    int& bpc = s0.trace_bpc[mode][geo][ldsn == 10 ? 0 : (ldsn == 16 ? 1 : 2)];
-    if (bpc == 0) {
-        e = wf_dispatch(mode, geo, ldsn, true, bpc, a, WfBuffers{}, 0, 0, stream);
-        if (e != hipSuccess) return e;
-        if (bpc < 1) bpc = 1;
-    }
-    uint32_t trace_grid = (uint32_t)(bpc * cus);
-/* Shade blocks per CU (grid-stride over the queue). The continuing paths are appended in roughly the order
- * the blocks walk their chunks, so a small grid keeps the next queue close to the input order (coherent rays
- * for the next trace). Measured on c3: 4 -> 7.98 ms, 8 -> 8.13, 16 -> 8.56, 32 -> 8.98, one thread per slot ->
- * 8.97. */
-#ifndef WCPT_SHADE_BLOCKS_PER_CU
-#define WCPT_SHADE_BLOCKS_PER_CU 4
-#endif
-    /* 0: one thread per path slot (no grid-stride loop) */
-    const uint32_t P = a.W * a.rows;
-    const uint32_t shade_grid = WCPT_SHADE_BLOCKS_PER_CU > 0 ? (uint32_t)(cus * WCPT_SHADE_BLOCKS_PER_CU)
-                                                             : (P + dev::kShadeBlock - 1) / dev::kShadeBlock;
+    /* the instance whose occupancy sizes the trace grid, and the persistent one's where the launch may take it */
     sort_rays = sort_rays && a.sd.drawCommandCount > 0;
-    /* the path-persistent trace (WCPT_OPTION_WF_PERSIST): one sample per pixel on the fast layout, and by default only
-     * where the frame's paths about fit its resident lanes (row blocks): there the per-bounce
-     * launches each last as long as their slowest ray, and one launch that lets each path run on lasts as long as its
-     * slowest path (c3 135-row blocks 1.30 against 1.85 ms; the full c3 frame 6.64 against 4.55 ms,
-     * profiles/r05_persist_ab.log) */
-    const bool persist_ok = mode == kModeRender && geo == 2 && a.sd.samples == 1u && !sort_rays && a.wf_persist != 0;
-    if (persist_ok && s0.persist_bpc == 0) {
-        e = wf_persist_dispatch(WCPT_WF_PERSIST_GEO, true, s0.persist_bpc, a, WfBuffers{}, 0, stream);
-        if (e != hipSuccess) return e;
-        if (s0.persist_bpc < 1) s0.persist_bpc = 1;
-    }
-    const uint32_t persist_full = persist_ok ? (uint32_t)(s0.persist_bpc * cus) : 0u;
-    /* at most 1.4 paths per resident lane: the lanes freed by the first paths take the rest (7- / 6-way c3 splits at
-     * 1.13 / 1.32 paths per lane gain 7 % / 3 %, 5-way at 1.58 is flat, 4-way at 2.0 loses) */
-    const bool persist = persist_ok && (a.wf_persist > 0 || (uint64_t)a.W * a.rows * 5ull <= 64ull * 7ull * persist_full);
-    /* pipelines: the option's count, or (0, the default) for the path-persistent trace one when each frame joins its
-     * pipelines (its blocks measured 1.30 / 1.40 / 1.40 ms with 1 / 2 / 3) and two under the frame overlap, where a
-     * pipeline's persistent launch runs on into its next frame (c3 8-way shares, slowest of 8, region-timed: 8-row
-     * stripes 1.254 / 1.246 ms with one, 1.219 / 1.218 with two, 1.218 / 1.214 with three -- a third stream would sit
-     * past the four hardware queues beside a group's communication stream; profiles/r06_c3_persist_pipes.log); else 3
-     * when the frame holds at most 8 paths per resident trace lane -- the launches are short and their tails weigh, so
-     * a third chain overlaps them (c3 4.41-4.46 against 4.50-4.55 ms with two) -- and 2 on longer queues (c4 199.5
-     * against 197.9 ms with two; profiles/r05_pipes_ab.log) */
-    uint32_t K = (uint32_t)(pipes > kWfMaxPipes ? kWfMaxPipes : pipes);
-    if (pipes < 1) {
-        K = persist ? (overlap != 0 && mode == kModeRender ? 2u : 1u)
-                    : ((uint64_t)a.W * a.rows <= (uint64_t)WCPT_WF_FETCH_ONCE_RATIO * 64ull * trace_grid ? 3u : 2u);
-    }
-    if (sort_rays || mode == kModeDiag) K = 1; /* one sort scratch and one diagnostics block */
-    const uint32_t tiles = tilesX * tilesY;
-    if (K > tiles) K = tiles;
-    /* each pipeline's persistent trace grid holds 1/K of the resident-wave slots, so the K traces run side by side
-     * instead of the first one taking every slot and the others only filling its tail (c3 6.58 -> 6.16 ms with two
-     * pipelines; 5/8 or 3/4 of the slots per pipeline measured equal, 7/16 slower) */
-    if (K > 1) trace_grid = trace_grid / K > 0 ? trace_grid / K : 1u;
-    const uint32_t persist_grid = persist ? max(1u, persist_full / K) : 0u;
-    /* Frame overlap (WCPT_OPTION_FRAME_OVERLAP; the megakernel's in pt_kernels.hip launch_megakernel): pipeline j
-     * owns the tiles t % K == j, so while K and the frame's tiles stay, this render's pipelines need not wait for the
-     * previous render's other pipelines -- each continues on its own stream, and the context's stream is joined to
-     * them only when another entry point needs it (wf_join). On the per-bounce launches that recovers the frame's
-     * ragged end (c3: its three pipelines end 0.3-0.5 ms apart, profiles/r06_c3_frame_timeline.log). */
-    const bool cont = overlap != 0 && K > 1 && mode == kModeRender && w.pending &&
-                      w.pending_pipes == K && w.pending_W == a.W && w.pending_rows == a.rows &&
-                      w.pending_persist == (persist_grid != 0);
+    const WfVariant base = wf_variant_select(mode, a.sd.drawCommandCount, a.wf_fast, lds_stack);
+    WfFrameInputs in = {base, mode, a.W, a.rows, a.sd.samples, a.sd.maxBounceCount, a.wf_fetch, a.wf_persist, pipes,
+                        sort_rays, overlap, cus, 0, 0};
+    e = wf_occupancy(s0, base, in.trace_bpc);
+    if (e == hipSuccess && wf_persist_eligible(base, a.sd.samples, sort_rays, a.wf_persist))
+        e = wf_occupancy(s0, wf_persist_variant(), in.persist_bpc);
+    if (e != hipSuccess) return e;
+    const WfFramePlan plan = wf_frame_plan(in);
+    if (!plan.ok) return hipErrorInvalidValue;
+    if (plan.empty) return hipSuccess;
+    const uint32_t K = plan.K;
+
+    /* frame overlap: this render's pipelines continue behind the previous render's on their own streams, or the
+     * context's stream is joined to those first */
+    const bool cont = wf_frame_continues(
+        plan, mode, overlap, WfPending{w.pending, w.pending_pipes, w.pending_W, w.pending_rows, w.pending_persist});
     if (w.pending && !cont) {
         e = wf_join(w, stream);
         if (e != hipSuccess) return e;
     }
     e = wf_reserve_result(w, (uint64_t)a.W * a.rows);
     if (e != hipSuccess) return e;
-    WfBuffers bs[kWfMaxPipes];
-    if (K == 1) {
-        e = pipe_begin(a, mode, s0, s0, w.result, w.result + w.result_capacity, 0, 1, cus, stream, bs[0]);
-        if (e != hipSuccess) return e;
-        return pipe_iterate(a, mode, s0, 0, 1, sort_rays, ldsn, cus, trace_grid, shade_grid, persist_grid, stream, bs[0]);
-    }
-
     /* fork: pipelines 1..K-1 run on their own streams after everything already queued on the context's stream */
-    if (!w.fork) {
+    if (K > 1 && !w.fork) {
         e = hipEventCreateWithFlags(&w.fork, hipEventDisableTiming);
         if (e != hipSuccess) return e;
     }
@@ -1162,7 +1064,7 @@ hipError_t launch_wavefront(const LaunchArgs& a, int mode, WfPipes& w, int pipes
             if (e != hipSuccess) return e;
         }
     }
-    if (!cont) {
+    if (K > 1 && !cont) {
         e = hipEventRecord(w.fork, stream);
         if (e != hipSuccess) return e;
         for (uint32_t j = 1; j < K; j++) {
@@ -1170,19 +1072,23 @@ hipError_t launch_wavefront(const LaunchArgs& a, int mode, WfPipes& w, int pipes
             if (e != hipSuccess) return e;
         }
     }
+
+    /* the inits of every pipeline, then their iterations */
+    WfBuffers bs[kWfMaxPipes];
     hipError_t first = hipSuccess;
     for (uint32_t j = 0; j < K && first == hipSuccess; j++)
-        first = pipe_begin(a, mode, w.pipe[j], s0, w.result, w.result + w.result_capacity, j, K, cus, j == 0 ? stream : w.aux[j], bs[j]);
+        first = pipe_begin(a, base, plan, j, w.pipe[j], s0, w.result, w.result + w.result_capacity,
+                           j == 0 ? stream : w.aux[j], bs[j]);
     for (uint32_t j = 0; j < K && first == hipSuccess; j++)
-        first = pipe_iterate(a, mode, w.pipe[j], j, K, false, ldsn, cus, trace_grid, shade_grid, persist_grid,
-                             j == 0 ? stream : w.aux[j], bs[j]);
+        first = pipe_iterate(a, base, plan, j, w.pipe[j], sort_rays, cus, j == 0 ? stream : w.aux[j], bs[j]);
+    if (K == 1) return first;
     /* join: the context's stream continues after every pipeline (also after a failed enqueue) -- now, or with the
      * frame overlap when another entry point needs the stream (wf_join) */
     w.pending = true;
     w.pending_pipes = K;
     w.pending_W = a.W;
     w.pending_rows = a.rows;
-    w.pending_persist = persist_grid != 0;
+    w.pending_persist = plan.persist;
     if (!overlap || mode != kModeRender || first != hipSuccess) {
         e = wf_join(w, stream);
         if (e != hipSuccess && first == hipSuccess) first = e;
