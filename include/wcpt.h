@@ -42,7 +42,7 @@ extern "C" {
  *    wcpt_group_info gained issue_threads; wcpt_group_set_output reads `bytes` in every process. Later additions that
  *    keep the layouts and calls (no version step): WCPT_GROUP_TRANSPORT_DIRECT, WCPT_OPTION_PROFILE_REGION,
  *    WCPT_OPTION_WF_FETCH, WCPT_OPTION_WF_PIPES 0 (automatic, now the default), wcpt_bvh_refit,
- *    wcpt_bvh_refit_device. */
+ *    wcpt_bvh_refit_device, wcpt_wf_last_plan. */
 #define WCPT_ABI_VERSION 4
 
 /* ---- error codes (VkResult-compatible where a VkResult exists) ---------------------------------- */
@@ -502,6 +502,44 @@ int      wcpt_mk_split_stats(wcpt_context* ctx, uint64_t* renders);
 /* How many renders of the context ran on the kernels that walk a tiny tree, with the draw's tree classified as one
  * (WCPT_OPTION_MK_TINY_TREE), since it was created: a count of renders that selected the walk, not of waves. Host only. Added under ABI 4. */
 int      wcpt_mk_tiny_tree_stats(wcpt_context* ctx, uint64_t* renders);
+/* What the context's last wavefront launch did (wcpt_render or wcpt_render_counters on WCPT_KERNEL_WAVEFRONT): the plan
+ * of csrc/wf_plan.h as it was carried out, the inputs it was made from, and per pipeline the trace instance that was
+ * really launched. Read-only and host only: it queues nothing and joins nothing, so a frame-overlap continuation goes
+ * on. All zeros (launches == 0) before the first wavefront launch. Codes are csrc/wf_plan.h's wf_variant_code
+ * numbering: an instance's (count, diag, geo, ldsn, persist). Added under ABI 4. */
+#define WCPT_WF_MAX_PIPES 4
+#define WCPT_WF_NO_VARIANT 0xFFFFFFFFu /* variant_code of a pipeline whose trace was not launched */
+typedef struct wcpt_wf_pipe_info {
+    uint32_t variant_code; /* of the instance handed to the dispatcher at this pipeline's (last) trace launch */
+    uint32_t dispatches;   /* trace launches of this pipeline in this frame: iters per-bounce, 1 persistent */
+    uint32_t tiles;        /* 8x8 tiles of the pipeline, */
+    uint32_t paths;        /* its path slots */
+    uint32_t iters;        /* and the plan's trace/shade iterations */
+} wcpt_wf_pipe_info;
+typedef struct wcpt_wf_plan_info {
+    uint64_t launches;     /* wavefront launches of the context since it was created, this one included */
+    int32_t  mode;         /* 0 render, 1 counting, 2 diagnostics */
+    int32_t  ok;           /* 0: the frame's lanes or pixels do not fit 32 bits; nothing was launched */
+    int32_t  empty;        /* 1: no pixels; nothing was launched */
+    int32_t  persist;      /* 1: the pipelines ran the path-persistent trace */
+    uint32_t K;            /* pipelines */
+    uint32_t trace_grid;   /* waves of one pipeline's per-bounce trace */
+    uint32_t shade_grid;   /* blocks of the shade kernel */
+    uint32_t persist_grid; /* waves of one pipeline's persistent trace, 0 without it */
+    int32_t  continued;    /* 1: under the frame overlap the pipelines continued behind the previous frame's unjoined */
+    int32_t  sort;         /* 1: the ray sort ran (the option, and there are draws to sort by) */
+    wcpt_wf_pipe_info pipe[WCPT_WF_MAX_PIPES]; /* [0, K) */
+    /* the inputs the plan was made from */
+    uint32_t base_code;    /* of the instance the launch selected, whose occupancy sizes the trace grid */
+    uint32_t width, rows;  /* the context's rows of the frame */
+    uint32_t samples, max_bounce;
+    int32_t  wf_fetch, wf_persist, pipes; /* the options as the launch read them */
+    int32_t  overlap;      /* WCPT_OPTION_FRAME_OVERLAP as the runtime allowed it for this launch */
+    int32_t  cus;          /* compute units of the device */
+    int32_t  trace_bpc;    /* blocks per compute unit of the base instance */
+    int32_t  persist_bpc;  /* ... of the persistent instance; 0 where the launch was not eligible for it */
+} wcpt_wf_plan_info;
+int      wcpt_wf_last_plan(wcpt_context* ctx, wcpt_wf_plan_info* out);
 /* Same frame through the instrumented kernel: counts the reference algorithm's work.
  * Does not write the image. Synchronous. */
 int      wcpt_render_counters(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t materials,

@@ -73,6 +73,9 @@ _Static_assert(sizeof(wcpt_node) == 32, "Node");
 _Static_assert(sizeof(wcpt_draw_command) == 32, "DrawCommand");
 _Static_assert(sizeof(wcpt_counters) == 16 * 8, "counters (ABI 2)");
 _Static_assert(offsetof(wcpt_counters, ref_stack_overflow_segments) == 14 * 8, "reference-stack fields last");
+_Static_assert(sizeof(wcpt_wf_pipe_info) == 20 && sizeof(wcpt_wf_plan_info) == 176, "wavefront launch record");
+_Static_assert(offsetof(wcpt_wf_plan_info, mode) == 8 && offsetof(wcpt_wf_plan_info, pipe) == 48, "its plan fields");
+_Static_assert(offsetof(wcpt_wf_plan_info, base_code) == 128 && offsetof(wcpt_wf_plan_info, persist_bpc) == 172, "its inputs");
 _Static_assert(WCPT_PAYLOAD_RGB32F == 3 && WCPT_PAYLOAD_RGBA32F == 4 && WCPT_PAYLOAD_DISPLAY_RGBA8 == 8, "payloads");
 int main(void) {{ return 0; }}
 ''')
@@ -115,6 +118,22 @@ def test_counters_struct_matches_header():
     assert C.sizeof(wcpt._lib.Counters) == 128
     assert wcpt._lib.Counters.ref_stack_overflow_segments.offset == 14 * 8
     assert wcpt.COUNTER_FIELDS[-2:] == ("ref_stack_overflow_segments", "ref_stack_max")
+
+
+def test_wf_plan_info_matches_header():
+    """wcpt_wf_plan_info / wcpt_wf_pipe_info: the mirror has the header's fields in the header's order and sizes."""
+    text = open(HEADER).read()
+    for cname, mirror, size in (("wcpt_wf_pipe_info", wcpt._lib.WfPipeInfo, 20), ("wcpt_wf_plan_info", wcpt._lib.WfPlanInfo, 176)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), text, re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        names = []
+        for decl in re.findall(r"(?:u?int(?:32|64)_t|wcpt_wf_pipe_info)\s+([^;]+);", body):
+            names += [re.sub(r"\[.*\]", "", n).strip() for n in decl.split(",")]
+        assert names == [n for n, _ in mirror._fields_], cname
+        assert C.sizeof(mirror) == size
+    assert wcpt._lib.WF_MAX_PIPES == int(re.search(r"#define WCPT_WF_MAX_PIPES (\d+)", text).group(1))
+    assert wcpt._lib.WF_NO_VARIANT == int(re.search(r"#define WCPT_WF_NO_VARIANT (0x[0-9A-Fa-f]+)u", text).group(1), 16)
+    assert wcpt.lib.wcpt_wf_last_plan(None, None) == -1001
 
 
 def test_group_entry_points_reject_bad_arguments():

@@ -30,8 +30,10 @@ import pytest
 import wcpt
 import oracle
 
+import wf_record
 from test_gpu_mk_split import _closed_box
 from test_gpu_parity import assert_close, get_scene
+from test_wf_plan import shim  # noqa: F401  (fixture: wf_plan.h through its CPU shim)
 
 pytestmark = pytest.mark.gpu
 
@@ -169,6 +171,7 @@ class Rig:
     def __init__(self):
         self.ctx = wcpt.Context(0)
         self.devs = {}
+        self.wf_plans = (None, None)   # the launch records of the last wavefront render() and of its counting run
 
     def dev(self, name):
         if name not in self.devs:
@@ -195,9 +198,11 @@ class Rig:
             ctx.image_upload(init)
         sd = s.scene_data(W, H, max_bounce=bounces, samples=spp, frame=frame)
         ctx.render(sd, *dev.addresses())
+        rec = ctx.wf_last_plan() if kernel == WAVE else None
         ctx.sync()
         img = ctx.readback(rows)
         cnt = ctx.render_counters(sd, *dev.addresses()) if counters else None
+        self.wf_plans = (rec, ctx.wf_last_plan() if kernel == WAVE and counters else None)
         if layout:
             ctx.set_row_range(0, 0)
         return img, cnt
@@ -215,25 +220,32 @@ def rig():
     r.close()
 
 
-def sweep(rig, name, W, H, kernel, variations, twice=False):
-    """Each (option, value, samples) of `variations`, alone, from the defaults: the oracle's image and counters."""
+def sweep(rig, name, W, H, kernel, variations, twice=False, ran=None):
+    """Each (option, value, samples) of `variations`, alone, from the defaults: the oracle's image and counters. A row
+    may name `also`, a dict of further options it needs to reach what it is there for. ran(options, samples, what):
+    called after the row's first render, to assert what it launched."""
     try:
-        for opt, value, spp in variations:
+        for opt, value, spp, *also in variations:
             ref, rcnt, init = ref_frame(name, W, H, spp)
             assert_not_empty(name, W, H, rcnt)
+            opts = dict(also[0]) if also else {}
             if opt is not None:
-                rig.ctx.set_option(opt, value)
+                opts[opt] = value
+            for o, v in opts.items():
+                rig.ctx.set_option(o, v)
             try:
                 img, cnt = rig.render(name, W, H, kernel, spp=spp, init=init)
                 what = f"option {opt} = {value}, {spp} spp"
                 assert_exact(img, ref, what)
                 assert cnt == rcnt, what
+                if ran:
+                    ran(opts, spp, what)
                 if twice:
                     again, _ = rig.render(name, W, H, kernel, spp=spp, init=init, counters=False)
                     assert np.array_equal(_bits(again), _bits(img)), what
             finally:
-                if opt is not None:
-                    rig.ctx.set_option(opt, DEFAULTS[opt])
+                for o in opts:
+                    rig.ctx.set_option(o, DEFAULTS[o])
     finally:
         rig.restore()
 
@@ -382,7 +394,8 @@ def test_frame_overlap_of_split_renders_on_odd_tile_counts(W, H):
 WF_SWEEP = ([(None, None, 1), (None, None, 2)] +
             [(T.OPTION_WF_PIPES, k, 1) for k in (1, 2, 3, 4)] + [(T.OPTION_WF_PIPES, 4, 2)] +
             [(T.OPTION_WF_PERSIST, v, 1) for v in (0, 1)] +
-            [(T.OPTION_WF_FETCH, v, 1) for v in (0, 1)] +
+            # the option is the per-bounce trace's: frames this small take the persistent trace unless it is off
+            [(T.OPTION_WF_FETCH, v, 1, {T.OPTION_WF_PERSIST: 0}) for v in (0, 1)] +
             [(T.OPTION_SORT_RAYS, v, 1) for v in (0, 1)] +
             [(T.OPTION_WF_STACK, v, 1) for v in (10, 16, 24)] +
             [(T.OPTION_WF_REFILL, v, 1) for v in (1, 64)])
@@ -390,11 +403,44 @@ WF_SWEEP = ([(None, None, 1), (None, None, 2)] +
 
 @pytest.mark.parametrize("W,H", SIZES)
 @pytest.mark.parametrize("name", SCENES)
-def test_wavefront_small_frames(rig, name, W, H):
+def test_wavefront_small_frames(rig, shim, name, W, H):
     """The wavefront kernel: 1 to 4 pipelines (more pipelines than tiles: K clamped to the tiles), the path-persistent
     trace and the per-bounce launches, one and two fetch rounds, sorted rays, the three LDS stacks, refill at 1 and 64.
-    Each rendered twice with equal bits."""
-    sweep(rig, name, W, H, WAVE, WF_SWEEP, twice=True)
+    Each rendered twice with equal bits. Every row asserts from the launch record (wcpt_wf_last_plan) that the render
+    launched what the row names; a scene without a mesh runs GEO 0 whatever the options say."""
+    tiles = ((W + 7) // 8) * ((H + 7) // 8)
+
+    def ran(opts, spp, what):
+        rec, crec = rig.wf_plans
+        variants = wf_record.check(shim, rec)
+        counting = wf_record.check(shim, crec)
+        assert crec["launches"] == rec["launches"] + 1, what
+        assert (rec["mode"], rec["width"], rec["rows"], rec["samples"]) == (wf_record.RENDER, W, H, spp), (what, rec)
+        assert all(v[:2] == (0, 0) for v in variants) and all(v[:2] == (1, 0) and v[3:] == (10, 0) for v in counting), what
+        assert 1 <= rec["K"] <= tiles and sum(q["tiles"] for q in rec["pipe"]) == tiles, (what, rec)
+        if T.OPTION_WF_PIPES in opts:
+            assert rec["K"] == crec["K"] == min(opts[T.OPTION_WF_PIPES], tiles), (what, rec)
+        if not HAS_MESH[name]:
+            assert rec["persist"] == 0 and all(v == (0, 0, 0, 10, 0) for v in variants), (what, variants)
+            return
+        if spp > 1:
+            assert rec["persist"] == 0, (what, rec)
+        if T.OPTION_WF_PERSIST in opts and spp == 1:
+            assert rec["persist"] == opts[T.OPTION_WF_PERSIST], (what, rec)
+            assert all(v[4] == opts[T.OPTION_WF_PERSIST] for v in variants), (what, variants)
+        if T.OPTION_WF_FETCH in opts:
+            assert all(v == (0, 0, 2 if opts[T.OPTION_WF_FETCH] == 0 else 3, 10, 0) for v in variants), (what, variants)
+        if T.OPTION_SORT_RAYS in opts:
+            assert rec["sort"] == crec["sort"] == opts[T.OPTION_SORT_RAYS], (what, rec)
+            if opts[T.OPTION_SORT_RAYS]:
+                assert rec["K"] == crec["K"] == 1 and rec["persist"] == 0, (what, rec)
+        if T.OPTION_WF_STACK in opts:
+            stack = opts[T.OPTION_WF_STACK]
+            assert all(v[3] == stack for v in variants), (what, variants)
+            if stack != 10:
+                assert all(v == (0, 0, 1, stack, 0) for v in variants), (what, variants)
+
+    sweep(rig, name, W, H, WAVE, WF_SWEEP, twice=True, ran=ran)
 
 
 ROW_LAYOUTS = [

@@ -12,6 +12,8 @@ import wcpt
 from wcpt import scene as wscene
 from wcpt.dist import row_block
 import oracle
+import wf_record
+from test_wf_plan import shim  # noqa: F401  (fixture: wf_plan.h through its CPU shim)
 
 pytestmark = pytest.mark.gpu
 
@@ -43,8 +45,31 @@ def assert_close(img, ref, exact=True):
         assert same == 1.0, f"bit-exact fraction {same:.6f}"
 
 
+# the launch records (wcpt_wf_last_plan) of the last gpu_render on the wavefront kernel: its render's and its counting run's
+wf_plans = {"render": None, "counters": None}
+
+
+def wf_ran(shim, K=None, geo=None, persist=None):
+    """The last gpu_render's wavefront launches, by their records: each is the plan of the inputs it reports
+    (wf_record.check, through wf_plan.h), the counting run follows the render, and the render launched what is named:
+    K pipelines, every one on a GEO of `geo`, on the persistent trace or not. Returns (render's record, its instances)."""
+    rec, crec = wf_plans["render"], wf_plans["counters"]
+    variants = wf_record.check(shim, rec)
+    assert rec["mode"] == wf_record.RENDER and all(v[:2] == (0, 0) for v in variants), rec
+    assert crec["launches"] == rec["launches"] + 1 and crec["mode"] == wf_record.COUNT, (rec, crec)
+    assert all(v[:2] == (1, 0) and v[4] == 0 for v in wf_record.check(shim, crec)), crec
+    if K is not None:
+        assert rec["K"] == K, rec
+    if geo is not None:
+        assert all(v[2] in geo for v in variants), (variants, rec)
+    if persist is not None:
+        assert rec["persist"] == persist and all(v[4] == persist for v in variants), rec
+    return rec, variants
+
+
 def gpu_render(ctx, s, W, H, bounces=3, spp=1, frame=0, y0=0, rows=None, init=None, sd=None, kernel=None):
     dev = wcpt.DeviceScene(ctx, s)
+    wavefront = kernel == wcpt.KERNEL_WAVEFRONT
     ctx.set_kernel(wcpt.KERNEL_MEGAKERNEL if kernel is None else kernel)
     try:
         ctx.create_screen(W, H)
@@ -54,9 +79,11 @@ def gpu_render(ctx, s, W, H, bounces=3, spp=1, frame=0, y0=0, rows=None, init=No
         if init is not None:
             ctx.image_upload(init)
         ctx.render(sd, *dev.addresses())
+        wf_plans["render"] = ctx.wf_last_plan() if wavefront else None
         ctx.sync()
         img = ctx.readback(rows or H)
         cnt = ctx.render_counters(sd, *dev.addresses())
+        wf_plans["counters"] = ctx.wf_last_plan() if wavefront else None
     finally:
         ctx.set_row_range(0, 0)
         ctx.set_kernel(wcpt.KERNEL_MEGAKERNEL)
@@ -708,8 +735,9 @@ def test_stack_refs_match_oracle(gpu_ctx, kernel, refs):
 
 
 @pytest.mark.parametrize("refill", [1, 12, 20, 64])
-def test_wavefront_refill_thresholds(gpu_ctx, refill):
-    """The wavefront trace's refill threshold changes only the order rays are processed in."""
+def test_wavefront_refill_thresholds(gpu_ctx, shim, refill):
+    """The wavefront trace's refill threshold changes only the order rays are processed in. A set value governs the
+    per-bounce and the persistent trace alike; the record says which of them this frame took."""
     s = get_scene("atrium")
     gpu_ctx.set_option(wcpt._lib.OPTION_WF_REFILL, refill)
     try:
@@ -719,6 +747,8 @@ def test_wavefront_refill_thresholds(gpu_ctx, refill):
     ref, rcnt = oracle.render_scene(s, 80, 48, max_bounce=4, threads=8)
     assert_close(img, ref)
     assert cnt == rcnt
+    rec, variants = wf_ran(shim, geo=(2, 3))         # one draw on the fast layout
+    assert all(v[4] == rec["persist"] for v in variants)
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
@@ -815,7 +845,7 @@ def test_tile_orders_match_oracle(gpu_ctx, order, name, W, H, bounces, spp, rows
     ("atrium", 200, 120, 4, 1, 1, 40),      # a row block
     ("cornell", 24, 8, 2, 1, 0, None),      # 3 tiles: fewer tiles than pipelines at 4
 ])
-def test_wavefront_pipelines_match_oracle(gpu_ctx, pipes, name, W, H, bounces, spp, frame, rows):
+def test_wavefront_pipelines_match_oracle(gpu_ctx, shim, pipes, name, W, H, bounces, spp, frame, rows):
     """WCPT_OPTION_WF_PIPES = K: K wavefront pipelines on K streams (tile t in pipeline t % K) render exactly the
     oracle's image and count exactly its work."""
     s = get_scene(name)
@@ -829,6 +859,10 @@ def test_wavefront_pipelines_match_oracle(gpu_ctx, pipes, name, W, H, bounces, s
                              kernel=wcpt.KERNEL_WAVEFRONT)
     finally:
         gpu_ctx.set_option(wcpt._lib.OPTION_WF_PIPES, wcpt._lib.DEFAULT_WF_PIPES)
+    K = min(pipes, ((W + 7) // 8) * (((rows or H) + 7) // 8))           # the option, at most a tile each
+    rec, _ = wf_ran(shim, K=K)
+    assert wf_plans["counters"]["K"] == K and rec["pipes"] == pipes     # the counting run splits the same way
+    assert sum(q["tiles"] for q in rec["pipe"]) == ((W + 7) // 8) * (((rows or H) + 7) // 8)
     ref, rcnt = oracle.render_scene(s, W, H, max_bounce=bounces, samples=spp, frame=frame, y0=y0, rows=rows,
                                     image=init, threads=8)
     assert_close(img, ref)
@@ -836,7 +870,7 @@ def test_wavefront_pipelines_match_oracle(gpu_ctx, pipes, name, W, H, bounces, s
     assert cnt == rcnt
 
 
-def test_wavefront_pipelines_full_frame(gpu_ctx):
+def test_wavefront_pipelines_full_frame(gpu_ctx, shim):
     """1080p atrium frame: 2 and 4 pipelines give the bit-identical frame of one pipeline, and the stream join
     orders a following readback after every pipeline."""
     s = get_scene("atrium")
@@ -847,12 +881,14 @@ def test_wavefront_pipelines_full_frame(gpu_ctx):
         one, c1 = gpu_render(gpu_ctx, s, W, H, bounces=4, frame=0, init=init, kernel=wcpt.KERNEL_WAVEFRONT)
     finally:
         gpu_ctx.set_option(wcpt._lib.OPTION_WF_PIPES, wcpt._lib.DEFAULT_WF_PIPES)
+    wf_ran(shim, K=1)
     for k in (2, 4):
         gpu_ctx.set_option(wcpt._lib.OPTION_WF_PIPES, k)
         try:
             img, ck = gpu_render(gpu_ctx, s, W, H, bounces=4, frame=0, init=init, kernel=wcpt.KERNEL_WAVEFRONT)
         finally:
             gpu_ctx.set_option(wcpt._lib.OPTION_WF_PIPES, wcpt._lib.DEFAULT_WF_PIPES)
+        wf_ran(shim, K=k)
         assert np.array_equal(img.view(np.uint32), one.view(np.uint32))
         assert ck == c1
 
@@ -864,22 +900,30 @@ def test_wavefront_pipelines_full_frame(gpu_ctx):
     ("default_dielectric", 48, 40, 3, 2, 7, None),
     ("atrium", 200, 120, 4, 2, 1, 40),      # a row block, two samples
 ])
-def test_wavefront_fetch_rounds_match_oracle(gpu_ctx, fetch, name, W, H, bounces, spp, frame, rows):
+def test_wavefront_fetch_rounds_match_oracle(gpu_ctx, shim, fetch, name, W, H, bounces, spp, frame, rows):
     """WCPT_OPTION_WF_FETCH = 0 / 1: the fast-layout trace with two fetch rounds per iteration (a leaf descent tested in
     the same iteration) and with one (interior and leaf fetches together, the descent tested next iteration) renders
-    exactly the oracle's image; auto picks one of them by queue length (small frames: one round)."""
+    exactly the oracle's image; auto picks one of them by queue length (small frames: one round). The record says which
+    instance every pipeline launched (the scene of spheres only has no fast layout: the option must leave it alone)."""
     s = get_scene(name)
     init = np.random.default_rng(11).uniform(0, 1, (rows or H, W, 4)).astype(np.float32)
     y0 = (H - rows) // 2 if rows else 0
     gpu_ctx.set_option(wcpt._lib.OPTION_WF_FETCH, fetch)
+    # the option is read by the per-bounce trace only: a one-sample frame this small would otherwise take the
+    # path-persistent trace, whose fetch rounds are fixed when it is compiled, with either value
+    gpu_ctx.set_option(wcpt._lib.OPTION_WF_PERSIST, 0)
     try:
         img, _ = gpu_render(gpu_ctx, s, W, H, bounces=bounces, spp=spp, frame=frame, y0=y0, rows=rows, init=init,
                             kernel=wcpt.KERNEL_WAVEFRONT)
     finally:
         gpu_ctx.set_option(wcpt._lib.OPTION_WF_FETCH, -1)
+        gpu_ctx.set_option(wcpt._lib.OPTION_WF_PERSIST, -1)
     ref, _ = oracle.render_scene(s, W, H, max_bounce=bounces, samples=spp, frame=frame, y0=y0, rows=rows,
                                  image=init, threads=8)
     assert_close(img, ref)
+    # two rounds: GEO 2, one round: GEO 3; default_dielectric has no mesh, so its frames are GEO 0 under either value
+    rec, _ = wf_ran(shim, geo=(0,) if not s.meshes else ((2,) if fetch == 0 else (3,)), persist=0)
+    assert rec["wf_fetch"] == fetch
 
 
 @pytest.mark.parametrize("persist", [0, 1])
@@ -890,7 +934,7 @@ def test_wavefront_fetch_rounds_match_oracle(gpu_ctx, fetch, name, W, H, bounces
     ("atrium", 200, 120, 4, 1, 40),      # a row block
     ("reference_init", 64, 48, 3, 0, None),
 ])
-def test_wavefront_persist_matches_oracle(gpu_ctx, persist, name, W, H, bounces, frame, rows):
+def test_wavefront_persist_matches_oracle(gpu_ctx, shim, persist, name, W, H, bounces, frame, rows):
     """WCPT_OPTION_WF_PERSIST = 0 / 1: the per-bounce trace + shade launches and the path-persistent trace (each lane
     runs its path's segments one after another and shades between them) render exactly the oracle's image."""
     s = get_scene(name)
@@ -905,9 +949,14 @@ def test_wavefront_persist_matches_oracle(gpu_ctx, persist, name, W, H, bounces,
     ref, _ = oracle.render_scene(s, W, H, max_bounce=bounces, samples=1, frame=frame, y0=y0, rows=rows,
                                  image=init, threads=8)
     assert_close(img, ref)
+    # a scene without a mesh (default_dielectric) has no fast layout: per-bounce GEO 0 whatever the option says
+    rec, variants = wf_ran(shim, persist=persist if s.meshes else 0, geo=None if s.meshes else (0,))
+    if rec["persist"]:
+        assert [q["variant_code"] for q in rec["pipe"]] == [wf_record.persist_code(shim)] * rec["K"]
+        assert all(q["dispatches"] == 1 for q in rec["pipe"])
 
 
-def test_wavefront_persist_full_frame_and_block(gpu_ctx):
+def test_wavefront_persist_full_frame_and_block(gpu_ctx, shim):
     """1080p atrium: the path-persistent trace forced on gives the bit-identical frame of the per-bounce launches, and
     so does a 135-row block (where it is the automatic choice); a bad option value is refused."""
     s = get_scene("atrium")
@@ -922,12 +971,13 @@ def test_wavefront_persist_full_frame_and_block(gpu_ctx):
                                       kernel=wcpt.KERNEL_WAVEFRONT)[0])
             finally:
                 gpu_ctx.set_option(wcpt._lib.OPTION_WF_PERSIST, -1)
+            wf_ran(shim, persist=persist)
         assert np.array_equal(out[0].view(np.uint32), out[1].view(np.uint32))
     with pytest.raises(wcpt.WcptError):
         gpu_ctx.set_option(wcpt._lib.OPTION_WF_PERSIST, 2)
 
 
-def test_wavefront_fetch_rounds_full_frame(gpu_ctx):
+def test_wavefront_fetch_rounds_full_frame(gpu_ctx, shim):
     """1080p atrium frame, 2 samples: one and two fetch rounds per trace iteration give the bit-identical frame, and a
     bad option value is refused."""
     s = get_scene("atrium")
@@ -941,6 +991,7 @@ def test_wavefront_fetch_rounds_full_frame(gpu_ctx):
                                   kernel=wcpt.KERNEL_WAVEFRONT)[0])
         finally:
             gpu_ctx.set_option(wcpt._lib.OPTION_WF_FETCH, -1)
+        wf_ran(shim, geo=(2,) if fetch == 0 else (3,), persist=0)
     assert np.array_equal(out[0].view(np.uint32), out[1].view(np.uint32))
     with pytest.raises(wcpt.WcptError):
         gpu_ctx.set_option(wcpt._lib.OPTION_WF_FETCH, 2)

@@ -21,7 +21,8 @@ trace <.., 3, 10> (WCPT_OPTION_WF_FETCH 1 or auto at this size) or the two-round
 WCPT_OPTION_PACKED_REFS 0 the layout is not fast and it takes <.., 1, 10>; WF_STACK 16 / 24 take <.., 1, 16> / <.., 1, 24>;
 the same mesh drawn twice takes <.., 0, 10>. Counting runs take <true, false, 1, 10> (two draws: <true, false, 0, 10>)
 whatever the options say. The megakernel takes PrivateStack<48> with WCPT_OPTION_STACK 0 and LdsStack<16, 32> with 1, in
-its render and its counting instances alike."""
+its render and its counting instances alike. The wavefront cases do not take this paragraph's word for it: every
+render and counting run asserts, from the launch record (wcpt_wf_last_plan), the instance each pipeline launched."""
 import copy
 
 import numpy as np
@@ -30,8 +31,10 @@ import pytest
 import wcpt
 import oracle
 
+import wf_record
 from deep_tree import deep_chain_scene
 from test_gpu_parity import assert_close, get_scene
+from test_wf_plan import shim  # noqa: F401  (fixture: wf_plan.h through its CPU shim)
 
 pytestmark = pytest.mark.gpu
 
@@ -51,6 +54,19 @@ CONFIGS = {
     "wf24": (WF, {T.OPTION_WF_STACK: 24}, 1),
     "wf_two_draws": (WF, {}, 2),
 }
+
+# the wf_trace instance (count, diag, geo, ldsn, persist) each wavefront configuration's renders must launch;
+# "persist": wf_persist_variant()
+WF_RENDERS = {
+    "wf10_persist": "persist",
+    "wf10_one_round": (0, 0, 3, 10, 0),
+    "wf10_two_rounds": (0, 0, 2, 10, 0),
+    "wf10_plain": (0, 0, 1, 10, 0),
+    "wf16": (0, 0, 1, 16, 0),
+    "wf24": (0, 0, 1, 24, 0),
+    "wf_two_draws": (0, 0, 0, 10, 0),
+}
+assert set(WF_RENDERS) == {n for n, c in CONFIGS.items() if c[0] == WF}
 
 _cache = {}
 
@@ -87,10 +103,12 @@ def untouched(levels):
 class Chains:
     """A context of its own set up as CONFIGS[name] says, with the chains it has uploaded."""
 
-    def __init__(self, name):
+    def __init__(self, name, shim):
+        self.name, self.shim = name, shim
         self.kernel, self.options, self.draws = CONFIGS[name]
         self.ctx = wcpt.Context(0)
         self.devs = {}
+        self.launches = 0
 
     def __enter__(self):
         self.ctx.set_kernel(self.kernel)
@@ -108,11 +126,30 @@ class Chains:
             self.devs[levels] = wcpt.DeviceScene(self.ctx, s)
         return (s.scene_data(W, H, max_bounce=BOUNCES),) + self.devs[levels].addresses()
 
+    def launched(self, want):
+        """the record of the wavefront launch just made: this launch's, the plan of its inputs, and every pipeline on
+        the instance `want`"""
+        if self.kernel != WF:
+            return
+        rec = self.ctx.wf_last_plan()
+        got = wf_record.check(self.shim, rec, launches=self.launches)
+        assert got == [want] * rec["K"], (self.name, got, want)
+        assert rec["persist"] == want[4] and (rec["width"], rec["rows"]) == (W, H)
+
     def render(self, levels):
-        self.ctx.render(*self.args(levels))      # raises if the render call itself reports anything
+        args = self.args(levels)
+        self.launches += 1
+        self.ctx.render(*args)                   # raises if the render call itself reports anything
+        want = WF_RENDERS.get(self.name)
+        self.launched(wf_record.decode(self.shim, wf_record.persist_code(self.shim)) if want == "persist" else want)
 
     def counters(self, levels):
-        return self.ctx.render_counters(*self.args(levels))
+        args = self.args(levels)
+        self.launches += 1
+        try:
+            return self.ctx.render_counters(*args)
+        finally:                                 # also when the call reports the overflow: the launch was made
+            self.launched((1, 0, 1 if self.draws == 1 else 0, 10, 0))
 
 
 def overflows(call):
@@ -122,9 +159,9 @@ def overflows(call):
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))
-def test_last_entry_fits(name):
+def test_last_entry_fits(shim, name):
     """levels = 48: the 48th entry is stored and popped; no status, image and counters exact."""
-    with Chains(name) as c:
+    with Chains(name, shim) as c:
         c.render(48)
         c.ctx.sync()
         img = c.ctx.readback()
@@ -137,11 +174,11 @@ def test_last_entry_fits(name):
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))
-def test_first_entry_that_does_not_fit_is_refused(name):
+def test_first_entry_that_does_not_fit_is_refused(shim, name):
     """levels = 49: the render returns success, the next sync reports the overflow once, pixels away from the chain are the
     oracle's, a 40-level frame afterwards is exact; the same through readback and through render_counters, which
     returns the error too (its counters are those of the cut-short traversal)."""
-    with Chains(name) as c:
+    with Chains(name, shim) as c:
         ctx = c.ctx
         c.render(49)
         overflows(ctx.sync)

@@ -12,7 +12,11 @@ depth other than 10 leaves the fast layout's GEO 2 / 3), each with its own LDS s
 that boundary at entry 10, 16 and 24. At depth 10 a one-draw frame on the fast layout takes what production takes there:
 GEO 2 / 3, or on frames this small the path-persistent trace; tests/test_gpu_stack_overflow.py selects each instance.
 
-The oracle's frames are computed once per module and shared; the tests read them and leave them unchanged."""
+The oracle's frames are computed once per module and shared; the tests read them and leave them unchanged.
+
+What a launch took is asserted, not assumed: _render keeps the launch record (wcpt_wf_last_plan) of every render and of
+the counting run, and _ran holds them against the plan of their own inputs (wf_record.check) and against what the test
+is there for -- one pipeline under the sort, the 16- and 24-entry instances."""
 import contextlib
 import copy
 
@@ -24,8 +28,10 @@ import oracle
 from wcpt import scene as wscene
 
 import tiny_scenes as ts
+import wf_record
 from deep_tree import deep_chain_scene
 from test_gpu_parity import _variant, assert_close, get_scene
+from test_wf_plan import shim  # noqa: F401  (fixture: wf_plan.h through its CPU shim)
 
 pytestmark = pytest.mark.gpu
 
@@ -97,20 +103,30 @@ def _ref(name, W, H, bounces, spp=1, frame=0, y0=0, rows=None):
     return _refs[key]
 
 
+_last = {"renders": [], "counters": None}   # the launch records of the last _render
+
+
 def _render(ctx, name, W, H, bounces, spp=1, frame=0, y0=0, rows=None, counters=True):
     """One wavefront frame of `name` on a new screen of ctx (progressive: the frames 0..frame), and its counters."""
     s = _scene(name)
     dev = wcpt.DeviceScene(ctx, s)
     ctx.set_kernel(WF)
+    _last.update(renders=[], counters=None)
     try:
         ctx.create_screen(W, H)
         ctx.set_row_range(y0, rows or 0)
+        first = ctx.wf_last_plan()["launches"] + 1
         for f in range(frame + 1):
             sd = s.scene_data(W, H, max_bounce=bounces, samples=spp, frame=f)
             ctx.render(sd, *dev.addresses())
+            _last["renders"].append(ctx.wf_last_plan())
         ctx.sync()
         img = ctx.readback(rows or H)
         cnt = ctx.render_counters(sd, *dev.addresses()) if counters else None
+        if counters:
+            _last["counters"] = ctx.wf_last_plan()
+        recs = _last["renders"] + ([_last["counters"]] if counters else [])
+        assert [r["launches"] for r in recs] == list(range(first, first + len(recs)))   # each record is of its launch
     finally:
         ctx.set_row_range(0, 0)
         ctx.set_kernel(wcpt.KERNEL_MEGAKERNEL)
@@ -125,6 +141,28 @@ def _check(ctx, case):
     assert cnt == rcnt
 
 
+def _ran(shim, sort=None, one_pipeline=False, ldsn=None, geo=None, persist=None):
+    """The last _render's launches, by their records: each holds the plan of its inputs, and what is named here. `ldsn`
+    and `geo` are of the render launches (the counting instances have one stack and no fast layout)."""
+    recs = _last["renders"] + ([_last["counters"]] if _last["counters"] else [])
+    assert _last["renders"]
+    for rec in recs:
+        variants = wf_record.check(shim, rec)
+        render = rec["mode"] == wf_record.RENDER
+        assert all(v[0] == (0 if render else 1) for v in variants), rec
+        if sort is not None:
+            assert rec["sort"] == sort, rec
+        if one_pipeline:
+            assert rec["K"] == 1, rec
+        if persist is not None and render:
+            assert rec["persist"] == persist, rec
+        if ldsn is not None:
+            assert all(v[3] == (ldsn if render else 10) for v in variants), (variants, rec)
+        if geo is not None and render:
+            assert all(v[2] in geo for v in variants), (variants, rec)
+    return recs
+
+
 # ---- WCPT_OPTION_SORT_RAYS ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", [
     ("cornell", 40, 24, 3, 1),               # P = 960 slots: hipCUB's small-input path
@@ -137,11 +175,15 @@ def _check(ctx, case):
     ("strip4", 40, 24, 3, 1),                # a root over two leaves, 0.15 wide on x
     ("flat4", 40, 24, 3, 1),                 # the same with no extent on x: wf_sort_keys' `ext > 0 ? ... : 0`
 ], ids=lambda c: "-".join(str(v) for v in c))
-def test_sorted_frames_match_oracle(gpu_ctx, case):
+def test_sorted_frames_match_oracle(gpu_ctx, shim, case):
     """Image and counters of a sorted frame equal the oracle's (render: wf_trace<false,...> reads b.order; counters:
-    wf_trace<true,...> reads it too)."""
+    wf_trace<true,...> reads it too). The sort ran, on one pipeline -- but for the scene with nothing to sort by."""
     with options(gpu_ctx, sort_rays=1):
         _check(gpu_ctx, case)
+    if case[0] == "cornell:no_meshes":
+        _ran(shim, sort=0, geo=(0,))
+    else:
+        _ran(shim, sort=1, one_pipeline=True, persist=0, geo=(0,) if case[0].endswith("two_draws") else (1, 2, 3))
     if case[0] in ("strip4", "flat4"):       # the boxes are what the case says they are
         root = _scene(case[0]).meshes[0].nodes[0]
         assert (root["max"][0] - root["min"][0] == 0.0) == (case[0] == "flat4")
@@ -159,15 +201,19 @@ def test_sort_scratch_regrows():
 
 @pytest.mark.parametrize("extra", [{"wf_pipes": 3}, {"wf_persist": 1}, {"wf_pipes": 3, "wf_persist": 1}, {"wf_fetch": 0},
                                    {"wf_fetch": 1}], ids=lambda e: "-".join(f"{k}{v}" for k, v in e.items()))
-def test_sort_with_pipelines_and_persist(gpu_ctx, extra):
+def test_sort_with_pipelines_and_persist(gpu_ctx, shim, extra):
     """With the sort on, wf_frame_plan (wf_plan.h) gives one pipeline whatever WCPT_OPTION_WF_PIPES says (one sort scratch)
     and never the path-persistent trace (wf_persist_eligible needs an unsorted render); either fetch-round instance reads the order. The
     frame is the oracle's."""
     with options(gpu_ctx, sort_rays=1, **extra):
         _check(gpu_ctx, ("cornell", 200, 150, 3, 1))
+    recs = _ran(shim, sort=1, one_pipeline=True, persist=0,
+                geo={0: (2,), 1: (3,)}.get(extra.get("wf_fetch"), (2, 3)))   # Cornell is on the fast layout
+    assert all(r["pipes"] == extra.get("wf_pipes", T.DEFAULT_WF_PIPES) and r["wf_persist"] == extra.get("wf_persist", -1)
+               for r in recs)
 
 
-def test_sort_row_range_then_stripes(gpu_ctx):
+def test_sort_row_range_then_stripes(gpu_ctx, shim):
     """A row block, then interleaved stripes of the same screen, sorted: image and counters equal the oracle's of
     those rows (the stripes': the oracle's blocks of each stripe, counters summed, the deepest stack their maximum)."""
     name, W, H, b = "cornell", 200, 150, 3
@@ -182,9 +228,13 @@ def test_sort_row_range_then_stripes(gpu_ctx):
             gpu_ctx.set_row_stripes(y_first, rows, stripe, period)
             sd = s.scene_data(W, H, max_bounce=b)
             gpu_ctx.render(sd, *dev.addresses())
+            rec = gpu_ctx.wf_last_plan()
             gpu_ctx.sync()
             img = gpu_ctx.readback(rows)
             cnt = gpu_ctx.render_counters(sd, *dev.addresses())
+            for r in (rec, gpu_ctx.wf_last_plan()):     # the stripes' rows, sorted, on one pipeline
+                wf_record.check(shim, r)
+                assert (r["sort"], r["K"], r["persist"], r["width"], r["rows"]) == (1, 1, 0, W, rows)
         finally:
             gpu_ctx.set_row_range(0, 0)
             gpu_ctx.set_kernel(wcpt.KERNEL_MEGAKERNEL)
@@ -195,15 +245,18 @@ def test_sort_row_range_then_stripes(gpu_ctx):
     assert cnt == want
 
 
-def test_sort_progressive_frames(gpu_ctx):
+def test_sort_progressive_frames(gpu_ctx, shim):
     """Frames 0, 1, 2 accumulated with the sort on equal the oracle's accumulation after each."""
     for frame in (0, 1, 2):
         with options(gpu_ctx, sort_rays=1):
             _check(gpu_ctx, ("cornell", 40, 24, 3, 1, frame))
+        assert len(_ran(shim, sort=1, one_pipeline=True, persist=0)) == frame + 2
 
 
-def test_sort_diagnostics_counters(gpu_ctx):
-    """The diagnostics build (wf_trace<true, true, ...>) with the sort on: its base fields are the plain counters."""
+def test_sort_diagnostics_counters(gpu_ctx, shim):
+    """The diagnostics build (wf_trace<true, true, ...>) with the sort on: its base fields are the plain counters, its
+    lane steps the work counters they are counted beside (wf_trace: simd_step next to interior_visits++, next to
+    triangle_tests++ and where a lane takes a queued ray), and the record names the one-draw diagnostics instance."""
     name, W, H, b = "cornell", 200, 150, 3
     s = _scene(name)
     dev = wcpt.DeviceScene(gpu_ctx, s)
@@ -213,13 +266,23 @@ def test_sort_diagnostics_counters(gpu_ctx):
         sd = s.scene_data(W, H, max_bounce=b)
         with options(gpu_ctx, sort_rays=1):
             cnt = gpu_ctx.render_counters(sd, *dev.addresses())
+            crec = gpu_ctx.wf_last_plan()
             dcnt = gpu_ctx.render_counters(sd, *dev.addresses(), diagnostics=True)
+            drec = gpu_ctx.wf_last_plan()
     finally:
         gpu_ctx.set_kernel(wcpt.KERNEL_MEGAKERNEL)
         dev.free()
     assert cnt == _ref(name, W, H, b)[1]
     assert {k: dcnt[k] for k in cnt} == cnt
     assert all(dcnt[k] > 0 for k in T.DIAG_FIELDS)
+    assert drec["launches"] == crec["launches"] + 1
+    assert wf_record.check(shim, crec) == [(1, 0, 1, 10, 0)] and (crec["mode"], crec["sort"]) == (wf_record.COUNT, 1)
+    assert wf_record.check(shim, drec) == [(1, 1, 1, 10, 0)] and (drec["mode"], drec["sort"]) == (wf_record.DIAG, 1)
+    assert dcnt["lane_interior_steps"] == cnt["interior_visits"]
+    assert dcnt["lane_triangle_steps"] == cnt["triangle_tests"]
+    assert dcnt["lane_segment_steps"] == cnt["segments"]
+    for phase in ("interior", "triangle", "segment"):
+        assert dcnt[f"wave_{phase}_steps"] <= dcnt[f"lane_{phase}_steps"] <= 64 * dcnt[f"wave_{phase}_steps"]
 
 
 # ---- WCPT_OPTION_WF_STACK ----------------------------------------------------------------------------------------------
@@ -233,17 +296,25 @@ STACK_CASES = [
 
 @pytest.mark.parametrize("case", STACK_CASES, ids=lambda c: "-".join(str(v) for v in c))
 @pytest.mark.parametrize("stack", [10, 16, 24])
-def test_lds_stack_depths_match_oracle(gpu_ctx, stack, case):
+def test_lds_stack_depths_match_oracle(gpu_ctx, shim, stack, case):
     with options(gpu_ctx, wf_stack=stack):
         _check(gpu_ctx, case)
+    if case[0].endswith("two_draws"):
+        _ran(shim, ldsn=10, geo=(0,), persist=0)         # GEO 0 has the 10-entry stack only
+    elif stack == 10:
+        _ran(shim, ldsn=10, geo=(1, 2, 3))
+    else:
+        _ran(shim, ldsn=stack, geo=(1,), persist=0)      # <false, false, 1, 16> / <.., 1, 24>
     if case[0].startswith("chain40"):
         assert _ref(*case)[1]["ref_stack_max"] == 41
 
 
-def test_lds_stack_16_sorted(gpu_ctx):
+def test_lds_stack_16_sorted(gpu_ctx, shim):
     with options(gpu_ctx, wf_stack=16, sort_rays=1):
         _check(gpu_ctx, STACK_CASES[0])
+        _ran(shim, sort=1, one_pipeline=True, ldsn=16, geo=(1,), persist=0)
         _check(gpu_ctx, ("cornell", 200, 150, 3, 1))
+        _ran(shim, sort=1, one_pipeline=True, ldsn=16, geo=(1,), persist=0)
 
 
 def test_lds_stack_refused_values(gpu_ctx):

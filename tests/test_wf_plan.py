@@ -5,52 +5,21 @@ iterations -- against pinned cases and against tests/wf_plan_cases.py, a plain P
 that held these rules before. A wrong rule here renders no wrong pixel: it is a silent slowdown, or a test that quietly
 runs another instance, so this is where it is caught."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
 import wf_plan_cases as model
+import wf_record
 from wf_plan_cases import RENDER, COUNT, DIAG
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEAD = ("ok", "empty", "persist", "W", "rows", "K", "trace_grid", "shade_grid", "persist_grid")
 PIPE = ("tiles", "total", "paths", "init_grid", "geo", "iters")
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = tmp_path_factory.mktemp("wfp") / "libwf_plan_shim.so"
-    src = os.path.join(ROOT, "tests", "wf_plan_shim.cpp")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", src, "-o", str(out)], check=True)
-    lib = ctypes.CDLL(str(out))
-    u32, u64, i = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
-    ints, i64s, u32s = ctypes.POINTER(i), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(u32)
-    lib.wfp_codes.restype = u32
-    lib.wfp_max_pipes.restype = i
-    lib.wfp_decode.argtypes = [u32, ints]
-    lib.wfp_decode.restype = None
-    lib.wfp_code.argtypes = [ints]
-    lib.wfp_code.restype = u32
-    lib.wfp_built.argtypes = [ints]
-    lib.wfp_built.restype = i
-    lib.wfp_select.argtypes = [i, u32, i, i, ints]
-    lib.wfp_select.restype = None
-    lib.wfp_persist_variant.argtypes = [ints]
-    lib.wfp_persist_variant.restype = None
-    lib.wfp_persist_eligible.argtypes = [ints, u32, i, i]
-    lib.wfp_persist_eligible.restype = i
-    lib.wfp_short_queue.argtypes = [u64, u32]
-    lib.wfp_short_queue.restype = i
-    lib.wfp_iterations.argtypes = [i, u32, u32]
-    lib.wfp_iterations.restype = u32
-    lib.wfp_share.argtypes = [u32, u32, u32, u32, u32s]
-    lib.wfp_share.restype = None
-    lib.wfp_plan.argtypes = [i64s, i64s]
-    lib.wfp_plan.restype = None
-    lib.wfp_continues.argtypes = [i64s, i, i, u32s]
-    lib.wfp_continues.restype = i
-    return lib
+    """tests/wf_plan_shim.cpp built with g++ and loaded: once per process, also for the GPU modules that import this."""
+    return wf_record.shim_library(lambda: tmp_path_factory.mktemp("wfp"))
 
 
 def _v(fields):
@@ -398,3 +367,129 @@ def test_continuation_needs_every_condition(shim):
                         (1, 3, kw["W"], kw["rows"], 1), (0, want["K"], kw["W"], kw["rows"], int(want["persist"]))):
             assert _continues(shim, kw, kw["mode"], kw["overlap"], pending) == \
                 model.continues(want, kw["mode"], kw["overlap"], *pending)
+
+
+# ---- the launch record (wcpt_wf_last_plan) and the model the GPU tests hold it against ------------------------------
+
+def _record(shim, launches=1, continued=0, **over):
+    """A record as launch_wavefront would fill it for the plan of these inputs: made up, no device involved."""
+    kw = dict(BASE, **over)
+    p = _plan(shim, **over)
+    base = _select(shim, kw["mode"], kw["draws"], kw["fast"], kw["lds_stack"])
+    rec = dict(launches=launches, mode=kw["mode"], ok=int(p["ok"]), empty=int(p["empty"]), persist=int(p["persist"]),
+               K=p["K"], trace_grid=p["trace_grid"], shade_grid=p["shade_grid"], persist_grid=p["persist_grid"],
+               continued=continued, sort=1 if (kw["sort"] and kw["draws"] > 0) else 0,
+               base_code=wf_record.code_of(shim, base), width=kw["W"], rows=kw["rows"], samples=kw["samples"],
+               max_bounce=kw["max_bounce"], wf_fetch=kw["wf_fetch"], wf_persist=kw["wf_persist"], pipes=kw["pipes"],
+               overlap=kw["overlap"], cus=kw["cus"], trace_bpc=kw["trace_bpc"], persist_bpc=kw["persist_bpc"])
+    rec["pipe"] = [dict(variant_code=wf_record.code_of(shim, q["variant"]), dispatches=1 if p["persist"] else q["iters"],
+                        tiles=q["tiles"], paths=q["paths"], iters=q["iters"]) for q in p["pipe"]]
+    return rec
+
+
+RECORDS = (dict(), dict(W=3840, rows=2160), dict(rows=135), dict(rows=135, overlap=0), dict(W=52, rows=44, pipes=4, samples=2),
+           dict(W=52, rows=44, wf_persist=1, pipes=2), dict(W=52, rows=44, mode=DIAG, draws=2, pipes=3),
+           dict(W=52, rows=44, mode=COUNT, pipes=3), dict(W=52, rows=44, lds_stack=24, pipes=3),
+           dict(W=52, rows=44, draws=0, pipes=4), dict(W=9, rows=8, pipes=4), dict(sort=1, pipes=3))
+
+
+def test_record_layout_matches_the_mirror(shim):
+    """wcpt_wf_plan_info as g++ lays it out is the ctypes mirror's: size and the offsets of a field of every group."""
+    import ctypes as C
+    from wcpt._lib import WfPipeInfo, WfPlanInfo
+    out = (C.c_uint32 * 9)()
+    shim.wfp_record_layout(out)
+    assert list(out) == [C.sizeof(WfPlanInfo), WfPlanInfo.launches.offset, WfPlanInfo.mode.offset, WfPlanInfo.K.offset,
+                         WfPlanInfo.continued.offset, WfPlanInfo.pipe.offset, WfPlanInfo.pipe.offset + C.sizeof(WfPipeInfo),
+                         WfPlanInfo.base_code.offset, WfPlanInfo.persist_bpc.offset]
+    assert C.sizeof(WfPlanInfo) == 176 and C.sizeof(WfPipeInfo) == 20 and shim.wfp_max_pipes() == 4
+
+
+def test_record_round_trip(shim):
+    """dict -> C record -> dict keeps every field (what the helpers rely on)."""
+    rec = _record(shim, launches=7, continued=1, W=52, rows=44, pipes=3)
+    assert wf_record.to_struct(rec).as_dict() == rec
+
+
+@pytest.mark.parametrize("over", RECORDS, ids=[str(i) for i in range(len(RECORDS))])
+def test_record_model_accepts_a_true_record(shim, over):
+    rec = _record(shim, **over)
+    assert wf_record.mismatches(shim, rec) == []
+    codes = wf_record.check(shim, rec, launches=1)
+    assert codes == [q["variant"] for q in _plan(shim, **over)["pipe"]]
+
+
+@pytest.mark.parametrize("over", RECORDS, ids=[str(i) for i in range(len(RECORDS))])
+def test_record_model_names_every_wrong_field(shim, over):
+    """One field at a time made wrong -- a plan field, a pipeline's field, an input the plan depends on: the model says
+    which (for an input: the plan fields that no longer follow from it)."""
+    good = _record(shim, **over)
+    for f in wf_record.PLAN_FIELDS:
+        bad = dict(good, **{f: good[f] + 1})
+        assert f in wf_record.mismatches(shim, bad), f
+    for j in range(good["K"]):
+        for f in wf_record.PIPE_FIELDS:
+            bad = dict(good, pipe=[dict(q) for q in good["pipe"]])
+            bad["pipe"][j][f] += 1
+            assert wf_record.mismatches(shim, bad) == [f"pipe[{j}].{f}"], (j, f)
+    # another built instance in one pipeline: the slip between plan and launch this record exists to show
+    for other in sorted(wf_record.built_codes(shim) - {good["pipe"][0]["variant_code"]}):
+        bad = dict(good, pipe=[dict(q) for q in good["pipe"]])
+        bad["pipe"][0]["variant_code"] = other
+        assert wf_record.mismatches(shim, bad) == ["pipe[0].variant_code"]
+        with pytest.raises(AssertionError):
+            wf_record.check(shim, bad)
+    # a pipeline too few or too many
+    assert "pipe" in wf_record.mismatches(shim, dict(good, pipe=good["pipe"][:-1]))
+    # inputs: the grids follow cus and the occupancy, the iterations the bounces, the shares the frame
+    assert "shade_grid" in wf_record.mismatches(shim, dict(good, cus=good["cus"] + 1))
+    assert "trace_grid" in wf_record.mismatches(shim, dict(good, trace_bpc=good["trace_bpc"] * 2 + 1))
+    assert any(m.endswith(".iters") for m in wf_record.mismatches(shim, dict(good, max_bounce=good["max_bounce"] + 1)))
+    assert any(m.endswith(".paths") for m in wf_record.mismatches(shim, dict(good, width=good["width"] + 64)))
+    if good["persist"]:
+        assert "persist_grid" in wf_record.mismatches(shim, dict(good, persist_bpc=good["persist_bpc"] + 8))
+        assert "persist" in wf_record.mismatches(shim, dict(good, samples=2))
+        assert "persist" in wf_record.mismatches(shim, dict(good, sort=1))
+        assert "persist" in wf_record.mismatches(shim, dict(good, wf_persist=0))
+    # a base instance no launch selects
+    assert wf_record.mismatches(shim, dict(good, base_code=wf_record.persist_code(shim))) == ["base_code"]
+    assert wf_record.mismatches(shim, dict(good, base_code=shim.wfp_codes())) == ["base_code"]
+
+
+def test_record_mode_and_sort_fix_the_pipelines(shim):
+    rec = _record(shim, W=52, rows=44, pipes=3)
+    assert rec["K"] == 3
+    assert "K" in wf_record.mismatches(shim, dict(rec, mode=DIAG))
+    assert "K" in wf_record.mismatches(shim, dict(rec, sort=1))
+    assert "K" in wf_record.mismatches(shim, dict(rec, pipes=2))
+
+
+def test_record_decoder_and_the_unreachable_instance(shim, every):
+    for code, v in enumerate(every):
+        assert wf_record.decode(shim, code) == v and wf_record.code_of(shim, v) == code
+    built = wf_record.built_codes(shim)
+    assert {wf_record.decode(shim, c) for c in built} == model.BUILT
+    geo = shim.wfp_persist_geo()
+    assert geo in (2, 3) and wf_record.decode(shim, wf_record.persist_code(shim)) == (0, 0, geo, 10, 1)
+    # the persistent GEO is a compile-time choice: the other persistent instance is built and never launched
+    assert {wf_record.decode(shim, c) for c in wf_record.unreachable_codes(shim)} == {(0, 0, 5 - geo, 10, 1)}
+    assert len(built - wf_record.unreachable_codes(shim)) == 11
+
+
+def test_record_continuation_model(shim):
+    """wfp_record_continues: pending exactly after a render of several pipelines under the overlap, and then
+    wf_frame_continues' conditions."""
+    a = _record(shim, W=52, rows=44, pipes=3, overlap=2)
+    assert not wf_record.continues(shim, a, None)                          # nothing pending
+    assert wf_record.continues(shim, a, a)
+    assert not wf_record.continues(shim, a, dict(a, overlap=0))            # the frame before joined at its end
+    assert not wf_record.continues(shim, dict(a, overlap=0), a)
+    assert not wf_record.continues(shim, a, _record(shim, W=52, rows=44, pipes=2, overlap=2))   # K changed
+    assert not wf_record.continues(shim, a, _record(shim, W=60, rows=44, pipes=3, overlap=2))   # resized
+    assert not wf_record.continues(shim, a, _record(shim, W=52, rows=44, pipes=3, overlap=2, mode=COUNT))
+    assert not wf_record.continues(shim, _record(shim, W=52, rows=44, pipes=3, overlap=2, mode=COUNT), a)
+    one = _record(shim, W=52, rows=44, pipes=1, overlap=2)
+    assert not wf_record.continues(shim, one, one)
+    p = _record(shim, W=52, rows=44, pipes=2, overlap=2, wf_persist=1)
+    assert p["persist"] == 1 and wf_record.continues(shim, p, p)
+    assert not wf_record.continues(shim, p, _record(shim, W=52, rows=44, pipes=2, overlap=2, wf_persist=0))

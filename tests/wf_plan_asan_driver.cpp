@@ -4,13 +4,15 @@
 // invariants checked on each: the pipelines' shares partition the tiles, nothing is written past the K pipelines, every
 // grid is at least 1, whatever a pipeline launches is built. A signed overflow, an out-of-range shift or an index past
 // pipe[kWfMaxPipes] is a sanitizer report, which aborts the process; the checks below return 1.
+// The launch record's model (tests/wf_plan_shim.cpp wfp_record_expect and wfp_record_continues, what tests/wf_record.py
+// holds a GPU render's wcpt_wf_last_plan against) runs here too, on records filled the way launch_wavefront fills them:
+// the shim's source is part of this program, nothing is loaded.
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <random>
 
-#include "../wc-path-tracer_amd/csrc/wf_plan.h"
-
-using namespace wcpt;
+#include "wf_plan_shim.cpp" // includes include/wcpt.h and wc-path-tracer_amd/csrc/wf_plan.h
 
 static int failures = 0;
 #define CHECK(cond)                                                         \
@@ -24,6 +26,64 @@ static int failures = 0;
 static WfFrameInputs inputs(int mode, uint32_t draws, bool fast, int stack, uint32_t W, uint32_t rows)
 {
     return WfFrameInputs{wf_variant_select(mode, draws, fast, stack), mode, W, rows, 1u, 4u, -1, -1, 0, false, 1, 256, 32, 16};
+}
+
+/* the record launch_wavefront makes of a plan it carried out whole (pt_wavefront.hip wf_record, pipe_iterate) */
+static wcpt_wf_plan_info record_of(const WfFrameInputs& in, const WfFramePlan& p)
+{
+    wcpt_wf_plan_info r = {};
+    r.launches = 1;
+    r.mode = in.mode;
+    r.ok = p.ok;
+    r.empty = p.empty;
+    r.persist = p.persist;
+    r.K = p.K;
+    r.trace_grid = p.trace_grid;
+    r.shade_grid = p.shade_grid;
+    r.persist_grid = p.persist_grid;
+    r.sort = in.sort;
+    for (uint32_t j = 0; j < (uint32_t)kWfMaxPipes; j++) {
+        r.pipe[j].variant_code = WCPT_WF_NO_VARIANT;
+        if (j >= p.K) continue;
+        r.pipe[j].variant_code = wf_variant_code(wf_pipe_variant(p, in.base, j));
+        r.pipe[j].dispatches = p.persist ? 1u : p.pipe[j].iters;
+        r.pipe[j].tiles = p.pipe[j].tiles;
+        r.pipe[j].paths = p.pipe[j].paths;
+        r.pipe[j].iters = p.pipe[j].iters;
+    }
+    r.base_code = wf_variant_code(in.base);
+    r.width = in.W;
+    r.rows = in.rows;
+    r.samples = in.samples;
+    r.max_bounce = in.max_bounce;
+    r.wf_fetch = in.wf_fetch;
+    r.wf_persist = in.wf_persist;
+    r.pipes = in.pipes;
+    r.overlap = in.overlap;
+    r.cus = in.cus;
+    r.trace_bpc = in.trace_bpc;
+    r.persist_bpc = in.persist_bpc;
+    return r;
+}
+
+/* the record's model gives back a true record, tells a wrong instance, and continues where wf_frame_continues does */
+static void record_model(const WfFrameInputs& in, const WfFramePlan& p)
+{
+    static_assert(sizeof(wcpt_wf_plan_info) == 176, "no padding: the records are compared as bytes");
+    wcpt_wf_plan_info r = record_of(in, p), want;
+    CHECK(wfp_record_expect(&r, &want) == 1);
+    CHECK(std::memcmp(&r, &want, sizeof(r)) == 0);
+    if (p.ok && !p.empty) {
+        wcpt_wf_plan_info bad = r;
+        bad.pipe[p.K - 1u].variant_code ^= 1u; /* the counting twin of the instance */
+        CHECK(wfp_record_expect(&bad, &want) == 1 && std::memcmp(&bad, &want, sizeof(bad)) != 0);
+        CHECK(want.pipe[p.K - 1u].variant_code == r.pipe[p.K - 1u].variant_code);
+    }
+    CHECK(!wfp_record_continues(&r, nullptr));
+    CHECK((wfp_record_continues(&r, &r) != 0) == (p.ok && !p.empty && in.overlap != 0 && p.K > 1u && in.mode == kModeRender));
+    wcpt_wf_plan_info off = r;
+    off.base_code = kWfVariantCodes; /* no instance: refused, the output zeroed */
+    CHECK(wfp_record_expect(&off, &want) == 0 && want.launches == 0u && want.K == 0u);
 }
 
 /* what holds of every plan */
@@ -72,6 +132,7 @@ static void edges()
                 WfFrameInputs in = inputs(kModeRender, 1u, true, 0, W, rows);
                 in.pipes = pipes;
                 invariants(in, wf_frame_plan(in));
+                record_model(in, wf_frame_plan(in));
             }
     /* the last frame accepted, and the first refused by its lanes alone */
     CHECK(wf_frame_plan(inputs(kModeRender, 1u, true, 0, 8u, 8u * ((1u << 26) - 1u))).ok);
@@ -113,6 +174,7 @@ static void sweep(std::mt19937& rng)
         in.trace_bpc = pick({1, 8, 20, 32});
         in.persist_bpc = pick({1, 4, 16});
         invariants(in, wf_frame_plan(in));
+        if (it % 8 == 0) record_model(in, wf_frame_plan(in));
     }
 }
 

@@ -1,8 +1,10 @@
 // Test shim (CPU): exposes the wavefront renderer's instance list, selection and frame plan
 // (wc-path-tracer_amd/csrc/wf_plan.h, what launch_wavefront applies and pt_wavefront.hip's dispatcher instantiates) to
 // tests/test_wf_plan.py over ctypes. Built by the test with g++; no HIP involved.
+#include <cstddef>
 #include <cstdint>
 
+#include "../include/wcpt.h"
 #include "../wc-path-tracer_amd/csrc/wf_plan.h"
 
 using namespace wcpt;
@@ -77,6 +79,74 @@ extern "C" int wfp_continues(const int64_t* w, int mode, int overlap, const uint
     const WfPending q = {pending[0] != 0, pending[1], pending[2], pending[3], pending[4] != 0};
     return wf_frame_continues(p, mode, overlap, q) ? 1 : 0;
 }
+
+// ---- the launch record (include/wcpt.h wcpt_wf_plan_info, filled by launch_wavefront, read by wcpt_wf_last_plan) ----
+// Its layout, for the Python mirror: the size, then the offsets of launches, mode, K, continued, pipe, pipe[1], base_code,
+// persist_bpc.
+extern "C" void wfp_record_layout(uint32_t* out)
+{
+    out[0] = (uint32_t)sizeof(wcpt_wf_plan_info);
+    out[1] = (uint32_t)offsetof(wcpt_wf_plan_info, launches);
+    out[2] = (uint32_t)offsetof(wcpt_wf_plan_info, mode);
+    out[3] = (uint32_t)offsetof(wcpt_wf_plan_info, K);
+    out[4] = (uint32_t)offsetof(wcpt_wf_plan_info, continued);
+    out[5] = (uint32_t)offsetof(wcpt_wf_plan_info, pipe);
+    out[6] = (uint32_t)(offsetof(wcpt_wf_plan_info, pipe) + sizeof(wcpt_wf_pipe_info));
+    out[7] = (uint32_t)offsetof(wcpt_wf_plan_info, base_code);
+    out[8] = (uint32_t)offsetof(wcpt_wf_plan_info, persist_bpc);
+}
+static_assert(WCPT_WF_MAX_PIPES == kWfMaxPipes, "the record holds every pipeline");
+
+static WfFrameInputs record_inputs(const wcpt_wf_plan_info& r)
+{
+    return WfFrameInputs{wf_variant_decode(r.base_code), r.mode, r.width, r.rows, r.samples, r.max_bounce, r.wf_fetch,
+                         r.wf_persist, r.pipes, r.sort != 0, r.overlap, r.cus, r.trace_bpc, r.persist_bpc};
+}
+
+// The model a GPU test holds a record against: what wf_frame_plan and wf_pipe_variant make of the inputs that `rec`
+// reports, as a record. `launches` and `continued` are not the plan's and are copied (wfp_record_continues has the
+// latter). Returns 0 if the reported base instance is not built or its code out of range (then *out is zeroed).
+extern "C" int wfp_record_expect(const wcpt_wf_plan_info* rec, wcpt_wf_plan_info* out)
+{
+    *out = wcpt_wf_plan_info{};
+    if (rec->base_code >= kWfVariantCodes) return 0;
+    const WfFrameInputs in = record_inputs(*rec);
+    if (!wf_variant_built(in.base) || in.base.persist) return 0;
+    const WfFramePlan p = wf_frame_plan(in);
+    *out = *rec; // the inputs, launches, continued
+    out->ok = p.ok;
+    out->empty = p.empty;
+    out->persist = p.persist;
+    out->K = p.K;
+    out->trace_grid = p.trace_grid;
+    out->shade_grid = p.shade_grid;
+    out->persist_grid = p.persist_grid;
+    for (uint32_t j = 0; j < (uint32_t)kWfMaxPipes; j++) {
+        wcpt_wf_pipe_info& q = out->pipe[j];
+        q = wcpt_wf_pipe_info{WCPT_WF_NO_VARIANT, 0u, 0u, 0u, 0u};
+        if (j >= p.K) continue;
+        q.variant_code = wf_variant_code(wf_pipe_variant(p, in.base, j));
+        q.dispatches = p.persist ? 1u : p.pipe[j].iters;
+        q.tiles = p.pipe[j].tiles;
+        q.paths = p.pipe[j].paths;
+        q.iters = p.pipe[j].iters;
+    }
+    return 1;
+}
+
+// Whether the launch `rec` reports continues behind the launch `prev` reports (null: nothing is pending -- the first
+// launch, or another entry point joined the pipelines in between). A launch leaves its pipelines unjoined exactly when
+// it ran several of them as a render under the overlap (launch_wavefront's last lines).
+extern "C" int wfp_record_continues(const wcpt_wf_plan_info* rec, const wcpt_wf_plan_info* prev)
+{
+    WfPending q = {};
+    if (prev && prev->ok && !prev->empty && prev->K > 1u && prev->overlap != 0 && prev->mode == kModeRender)
+        q = WfPending{true, prev->K, prev->width, prev->rows, prev->persist != 0};
+    return wf_frame_continues(wf_frame_plan(record_inputs(*rec)), rec->mode, rec->overlap, q) ? 1 : 0;
+}
+
+// the build's persistent GEO (WCPT_WF_PERSIST_GEO): the other persistent instance is compiled but never selected
+extern "C" int wfp_persist_geo(void) { return WCPT_WF_PERSIST_GEO; }
 
 // The selection and a plan evaluated by the compiler: the functions are usable in constant expressions (the
 // dispatcher's `if constexpr (wf_variant_built(...))` needs that of the list). 1920x1080, one draw on the fast layout,

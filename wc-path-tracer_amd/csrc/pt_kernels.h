@@ -130,7 +130,9 @@ struct WfPipes {
     bool pending = false;
     uint32_t pending_pipes = 0, pending_W = 0, pending_rows = 0;
     bool pending_persist = false;
+    wcpt_wf_plan_info last = {};         /* what the last launch_wavefront did (wcpt_wf_last_plan); host memory only */
 };
+static_assert(WCPT_WF_MAX_PIPES == kWfMaxPipes, "wcpt_wf_plan_info holds every pipeline");
 hipError_t wf_join(WfPipes& w, hipStream_t stream);
 
 /* Megakernel launch state, per context. */

@@ -975,12 +975,16 @@ static hipError_t pipe_begin(const LaunchArgs& a, const WfVariant& base, const W
     return hipGetLastError();
 }
 
+/* `rec`: the pipeline's entry of the launch record (wcpt_wf_last_plan) -- the instance as it is handed to the
+ * dispatcher, noted at the call, so the record states what was launched and not what was planned. */
 static hipError_t pipe_iterate(const LaunchArgs& a, const WfVariant& base, const WfFramePlan& plan, uint32_t j, WfState& s,
-                               bool sort_rays, int cus, hipStream_t stream, WfBuffers b)
+                               bool sort_rays, int cus, hipStream_t stream, WfBuffers b, wcpt_wf_pipe_info& rec)
 {
     const WfVariant v = wf_pipe_variant(plan, base, j);
     if (plan.persist) { /* every segment in one launch */
         const WfTraceLaunch l = {a, b, plan.persist_grid, stream};
+        rec.variant_code = wf_variant_code(v);
+        rec.dispatches++;
         return wf_dispatch(v, &l, nullptr);
     }
     for (uint32_t it = 0; it < plan.pipe[j].iters; it++) {
@@ -991,6 +995,8 @@ static hipError_t pipe_iterate(const LaunchArgs& a, const WfVariant& base, const
             b.order = s.sort_order;
         }
         const WfTraceLaunch l = {a, b, plan.trace_grid, stream};
+        rec.variant_code = wf_variant_code(v);
+        rec.dispatches++;
         hipError_t e = wf_dispatch(v, &l, nullptr);
         if (e != hipSuccess) return e;
         if (base.count) launch_shade<true>(a, b, plan, stream);
@@ -1016,6 +1022,43 @@ hipError_t wf_join(WfPipes& w, hipStream_t stream)
     return first;
 }
 
+/* The launch record (wcpt_wf_last_plan): the plan and its inputs, once the plan is made. The pipelines' instances
+ * are noted where they are launched (pipe_iterate), the continuation where it is decided. */
+static void wf_record(wcpt_wf_plan_info& r, const WfFrameInputs& in, const WfFramePlan& plan)
+{
+    const uint64_t launches = r.launches + 1u;
+    r = wcpt_wf_plan_info{};
+    r.launches = launches;
+    r.mode = in.mode;
+    r.ok = plan.ok ? 1 : 0;
+    r.empty = plan.empty ? 1 : 0;
+    r.persist = plan.persist ? 1 : 0;
+    r.K = plan.K;
+    r.trace_grid = plan.trace_grid;
+    r.shade_grid = plan.shade_grid;
+    r.persist_grid = plan.persist_grid;
+    r.sort = in.sort ? 1 : 0;
+    for (uint32_t j = 0; j < (uint32_t)kWfMaxPipes; j++) {
+        r.pipe[j].variant_code = WCPT_WF_NO_VARIANT;
+        if (j >= plan.K) continue;
+        r.pipe[j].tiles = plan.pipe[j].tiles;
+        r.pipe[j].paths = plan.pipe[j].paths;
+        r.pipe[j].iters = plan.pipe[j].iters;
+    }
+    r.base_code = wf_variant_code(in.base);
+    r.width = in.W;
+    r.rows = in.rows;
+    r.samples = in.samples;
+    r.max_bounce = in.max_bounce;
+    r.wf_fetch = in.wf_fetch;
+    r.wf_persist = in.wf_persist;
+    r.pipes = in.pipes;
+    r.overlap = in.overlap;
+    r.cus = in.cus;
+    r.trace_bpc = in.trace_bpc;
+    r.persist_bpc = in.persist_bpc;
+}
+
 /* Every decision about the frame is wf_plan.h's (wf_variant_select, wf_frame_plan, wf_frame_continues); this function
  * asks the device what the plan needs and carries it out. */
 hipError_t launch_wavefront(const LaunchArgs& a, int mode, WfPipes& w, int pipes, bool sort_rays, int lds_stack,
@@ -1035,6 +1078,7 @@ hipError_t launch_wavefront(const LaunchArgs& a, int mode, WfPipes& w, int pipes
         e = wf_occupancy(s0, wf_persist_variant(), in.persist_bpc);
     if (e != hipSuccess) return e;
     const WfFramePlan plan = wf_frame_plan(in);
+    wf_record(w.last, in, plan);
     if (!plan.ok) return hipErrorInvalidValue;
     if (plan.empty) return hipSuccess;
     const uint32_t K = plan.K;
@@ -1043,6 +1087,7 @@ hipError_t launch_wavefront(const LaunchArgs& a, int mode, WfPipes& w, int pipes
      * context's stream is joined to those first */
     const bool cont = wf_frame_continues(
         plan, mode, overlap, WfPending{w.pending, w.pending_pipes, w.pending_W, w.pending_rows, w.pending_persist});
+    w.last.continued = cont ? 1 : 0;
     if (w.pending && !cont) {
         e = wf_join(w, stream);
         if (e != hipSuccess) return e;
@@ -1080,7 +1125,7 @@ hipError_t launch_wavefront(const LaunchArgs& a, int mode, WfPipes& w, int pipes
         first = pipe_begin(a, base, plan, j, w.pipe[j], s0, w.result, w.result + w.result_capacity,
                            j == 0 ? stream : w.aux[j], bs[j]);
     for (uint32_t j = 0; j < K && first == hipSuccess; j++)
-        first = pipe_iterate(a, base, plan, j, w.pipe[j], sort_rays, cus, j == 0 ? stream : w.aux[j], bs[j]);
+        first = pipe_iterate(a, base, plan, j, w.pipe[j], sort_rays, cus, j == 0 ? stream : w.aux[j], bs[j], w.last.pipe[j]);
     if (K == 1) return first;
     /* join: the context's stream continues after every pipeline (also after a failed enqueue) -- now, or with the
      * frame overlap when another entry point needs the stream (wf_join) */

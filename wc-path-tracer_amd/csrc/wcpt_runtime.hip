@@ -328,6 +328,15 @@ int wcpt_mk_tiny_tree_stats(wcpt_context* ctx, uint64_t* renders)
     return WCPT_SUCCESS;
 }
 
+/* no bind: reading the record must not join the pipelines it describes */
+int wcpt_wf_last_plan(wcpt_context* ctx, wcpt_wf_plan_info* out)
+{
+    if (!ctx) return set_error(nullptr, WCPT_ERROR_INVALID_HANDLE, "null context");
+    if (!out) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "null plan record");
+    *out = ctx->wf.last;
+    return WCPT_SUCCESS;
+}
+
 int wcpt_sync(wcpt_context* ctx)
 {
     int rc = bind(ctx);

@@ -12,7 +12,12 @@
  *    2 count     the counting build, GEO 0 and 1
  *    2 diag      ... with the SIMD step counters and the phase timers, GEO 0 and 1
  *    2 persist   the path-persistent render, GEO 2 and 3
- * All but render GEO 1 take the 10-entry stack. */
+ * All but render GEO 1 take the 10-entry stack.
+ * Eleven of the twelve can be launched. wf_persist_variant() fixes the persistent trace's GEO when the library is compiled
+ * (WCPT_WF_PERSIST_GEO, 3), so the persistent instance of the other GEO (2) is in the code object and no launch selects
+ * it: it is there for a build with the macro set the other way, which then leaves GEO 3 unreachable.
+ * tests/test_gpu_wf_variants.py launches the eleven, each asserted from the launch record (wcpt_wf_last_plan), and
+ * asserts that the twelfth is exactly the built set's remainder. */
 #ifndef WCPT_WF_PLAN_H
 #define WCPT_WF_PLAN_H
 

@@ -139,6 +139,33 @@ class GroupInfo(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+WF_MAX_PIPES = 4
+WF_NO_VARIANT = 0xFFFFFFFF  # WfPipeInfo.variant_code of a pipeline whose trace was not launched
+
+
+class WfPipeInfo(C.Structure):
+    """wcpt_wf_pipe_info (include/wcpt.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("variant_code", "dispatches", "tiles", "paths", "iters")]
+
+
+class WfPlanInfo(C.Structure):
+    """wcpt_wf_plan_info (include/wcpt.h): what the last wavefront launch did, and the inputs its plan was made from."""
+    _fields_ = ([("launches", C.c_uint64)] +
+                [(n, C.c_int32) for n in ("mode", "ok", "empty", "persist")] +
+                [(n, C.c_uint32) for n in ("K", "trace_grid", "shade_grid", "persist_grid")] +
+                [(n, C.c_int32) for n in ("continued", "sort")] +
+                [("pipe", WfPipeInfo * WF_MAX_PIPES)] +
+                [(n, C.c_uint32) for n in ("base_code", "width", "rows", "samples", "max_bounce")] +
+                [(n, C.c_int32) for n in ("wf_fetch", "wf_persist", "pipes", "overlap", "cus", "trace_bpc", "persist_bpc")])
+
+    def as_dict(self):
+        """Every field by name; `pipe` is the list of the K pipelines' dicts."""
+        out = {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "pipe"}
+        out["pipe"] = [{n: int(getattr(self.pipe[j], n)) for n, _ in WfPipeInfo._fields_}
+                       for j in range(min(out["K"], WF_MAX_PIPES))]
+        return out
+
+
 class BloomParams(C.Structure):
     """wcpt_bloom_params (include/wcpt.h): the callers' defaults are threshold 1.0, knee 0.1, 6 levels."""
     _fields_ = [("threshold", C.c_float), ("knee", C.c_float), ("levels", C.c_uint32), ("_pad", C.c_uint32)]
@@ -197,6 +224,7 @@ _PROTOTYPES = {
     "wcpt_primary_cache_stats": (_i, [_p, C.POINTER(_u64), C.POINTER(_u64)]),
     "wcpt_mk_split_stats": (_i, [_p, C.POINTER(_u64)]),
     "wcpt_mk_tiny_tree_stats": (_i, [_p, C.POINTER(_u64)]),
+    "wcpt_wf_last_plan": (_i, [_p, C.POINTER(WfPlanInfo)]),
     "wcpt_render_counters": (_i, [_p, _p, _u64, _u64, _u64, C.POINTER(Counters)]),
     "wcpt_read_diagnostics": (_i, [_p, C.POINTER(C.c_uint64), _u32]),
     "wcpt_profile_begin": (_i, [_p]),

@@ -13,7 +13,7 @@ import numpy as np
 
 from ._lib import (COUNTER_FIELDS, DRAW_COMMAND_DTYPE, GROUP_OPTION_ROW_STRIPE, GROUP_TRANSPORT_RCCL,
                    GROUP_UNIQUE_ID_BYTES, ARITH_EXACT, OPTION_ARITH, OPTION_DIAGNOSTICS,
-                   MATERIAL_DTYPE, NODE_DTYPE, SCENE_DATA_DTYPE, SPHERE_DTYPE, Camera, Counters, GroupInfo, WcptError, check, lib, ptr)
+                   MATERIAL_DTYPE, NODE_DTYPE, SCENE_DATA_DTYPE, SPHERE_DTYPE, Camera, Counters, GroupInfo, WcptError, WfPlanInfo, check, lib, ptr)
 from . import scene as _scene
 
 
@@ -202,6 +202,13 @@ class Context:
         n = C.c_uint64(0)
         self._chk(lib.wcpt_mk_tiny_tree_stats(self.h, C.byref(n)))
         return int(n.value)
+
+    def wf_last_plan(self) -> dict:
+        """wcpt_wf_last_plan: what the last wavefront launch did (WfPlanInfo.as_dict()). Host only: it joins nothing, so
+        reading it between renders leaves a frame-overlap continuation running."""
+        out = WfPlanInfo()
+        self._chk(lib.wcpt_wf_last_plan(self.h, C.byref(out)))
+        return out.as_dict()
 
     def render_counters(self, sd: np.ndarray, materials: int, spheres: int, draws: int,
                         diagnostics: bool = False) -> dict:
