@@ -681,6 +681,119 @@ def test_group_row_stripes_in_line_multi_sample_and_relayout(gpu_ctx, kernel):
             d.free()
 
 
+_WALK_SIZES = ((16, 17), (8, 20), (24, 33))
+_WALK_REFS = {}
+
+
+def _walk_reference(s, W, H, k):
+    """One context's image of frames 0..k-1 at W x H (one bounce), k even; each size is rendered once and shared."""
+    if not _WALK_REFS:
+        for (w, h) in _WALK_SIZES:
+            with wcpt.Context(0) as ctx:
+                dev = wcpt.DeviceScene(ctx, s)
+                ctx.create_screen(w, h)
+                for f in range(8):
+                    ctx.render(s.scene_data(w, h, max_bounce=1, frame=f), *dev.addresses())
+                    if f % 2:
+                        ctx.sync()
+                        _WALK_REFS[(w, h, f + 1)] = ctx.readback().copy()
+                dev.free()
+    return _WALK_REFS[(W, H, k)]
+
+
+@pytest.mark.parametrize("transport", [COPY, DIRECT])
+def test_group_layout_follows_every_change_on_one_group(gpu_ctx, transport):
+    """One group of 3 ranks (root 1) walked through sizes, stripes, formats and presenting off and on: the group keeps a
+    table of where every rank's rows go (group_layout.h), laid out again after every accepted change, and a stale table
+    would present rows of the previous layout. Two frames after each change; each presented frame equals one context's
+    of the frames accumulated since the screen was last laid out, and nothing is written past the frame. None of the
+    heights divides by 3; with 8-row stripes 17 rows leave rank 2 only the one-row short stripe, and 17 and 20 rows
+    give exactly as many stripes as ranks. Two changes are refused (15 rows and 16-row stripes on 20 rows both give 2
+    stripes for 3 ranks): the frames after them continue the layout in force."""
+    RGB, RGBA, RGBA8 = wcpt._lib.PAYLOAD_RGB32F, wcpt._lib.PAYLOAD_RGBA32F, wcpt._lib.PAYLOAD_DISPLAY_RGBA8
+    STRIPE = wcpt._lib.GROUP_OPTION_ROW_STRIPE
+    s = get_scene("cornell")
+    cap = 24 * 33 * 16
+    sentinel = np.full((cap + 4096) // 4, -7.0, np.float32)
+    with wcpt.Group([0, 0, 0], root=1, transport=transport) as g:
+        devs = [wcpt.DeviceScene(g.context(r), s) for r in range(3)]
+        addr = [list(a) for a in zip(*[d.addresses() for d in devs])]
+        root = g.context(1)
+        out = root.buffer_from(sentinel)
+        state = dict(W=0, H=0, fmt=RGB, frames=0)
+
+        def screen(W, H):
+            g.create_screen(W, H)
+            state.update(W=W, H=H, frames=0)                  # CreateScreen: the accumulation starts again
+
+        def stripe(rows):
+            g.set_option(STRIPE, rows)                        # lays the frame out again
+            state.update(frames=0)
+
+        def output(fmt):
+            g.set_output(fmt, root.buffer_address(out), cap)
+            state.update(fmt=fmt)
+
+        def two_frames(check, step):
+            W, H, fmt = state["W"], state["H"], state["fmt"]
+            root.buffer_upload(out, sentinel)                 # the group is idle: every check ends in a sync
+            for _ in range(2):
+                g.render(s.scene_data(W, H, max_bounce=1, frame=state["frames"]), *addr)
+                state["frames"] += 1
+            g.sync()
+            if not check:
+                return
+            raw = root.buffer_download(out, sentinel.nbytes)
+            nbytes = W * H * PB[fmt]
+            got = _as_frame(raw[:nbytes], fmt, W, H)
+            ref = _walk_reference(s, W, H, state["frames"])
+            if fmt == RGBA8:
+                assert np.array_equal(got, oracle.composite(ref)[1]), step
+            else:
+                assert np.array_equal(got.view(np.uint32), ref[..., :got.shape[2]].view(np.uint32)), step
+            assert raw[nbytes:] == sentinel.tobytes()[nbytes:], step
+
+        screen(16, 17)
+        output(RGB)
+        two_frames(True, "16x17 blocks RGB32F")
+        stripe(8)
+        two_frames(True, "16x17 stripes of 8 (8, 8, 1 rows)")
+        output(RGBA8)
+        two_frames(True, "16x17 stripes RGBA8")
+        screen(8, 20)
+        two_frames(True, "8x20 stripes of 8 (8, 8, 4 rows)")
+        with pytest.raises(wcpt.WcptError):
+            g.set_option(STRIPE, 16)                          # 2 stripes for 3 ranks: refused, stripes of 8 stay
+        two_frames(True, "8x20 after the refused stripe change")
+        stripe(0)
+        two_frames(True, "8x20 blocks RGBA8")
+        output(RGBA)
+        two_frames(True, "8x20 blocks RGBA32F")
+        g.set_output(0, 0, 0)
+        two_frames(False, "not presenting")
+        output(RGBA)
+        two_frames(True, "8x20 presenting again")
+        screen(24, 33)
+        two_frames(True, "24x33 blocks RGBA32F")
+        stripe(8)
+        two_frames(True, "24x33 stripes of 8")
+        with pytest.raises(wcpt.WcptError):
+            g.create_screen(24, 15)                           # 2 stripes for 3 ranks: refused, 24x33 stays
+        two_frames(True, "24x33 after the refused resize")
+        output(RGB)
+        two_frames(True, "24x33 stripes RGB32F")
+        stripe(0)
+        two_frames(True, "24x33 blocks RGB32F")
+        screen(16, 17)
+        two_frames(True, "16x17 again")
+        info = g.info()
+        g.set_output(0, 0, 0)
+        root.buffer_free(out)
+        for d in devs:
+            d.free()
+    assert info["broken"] == 0 and info["frames"] == 30
+
+
 @pytest.mark.parametrize("kernel", [wcpt.KERNEL_MEGAKERNEL, wcpt.KERNEL_WAVEFRONT])
 def test_context_row_stripes_and_frame_row_output(gpu_ctx, kernel):
     """wcpt_set_row_stripes on one context: its accumulation holds exactly the frame rows of the map, bit-identical to

@@ -45,6 +45,10 @@ enum Op : int32_t {
     kRecordSent = 7,    /* sent[buffer] recorded behind the rank's transfer                                     */
     kScatter = 8,       /* the root copies rank `peer`'s received stripes from staging to their frame rows        */
 };
+constexpr int kOps = 9;
+/* the ops' names, in the enum's order (the tools-only step timers of wcpt_group.hip print them) */
+constexpr const char* kOpNames[kOps] = {"wait_sent", "set_output", "render", "record_ready", "comm_wait_ready",
+                                        "send", "recv", "record_sent", "scatter"};
 
 enum Stream : int32_t { kRenderStream = 0, kCommStream = 1 };
 

@@ -137,6 +137,14 @@ inline LayoutRefusal layout_frame_block(const ScreenLayout& old, uint32_t width,
     return layout_last_row(next) >= height ? kLayoutPastFrame : kLayoutOk;
 }
 
+/* ---- the formats a frame's rows are presented in (wcpt.h WCPT_PAYLOAD_*: the gather output, the group's frame) ------- */
+
+enum PayloadFormat : uint32_t { kPayloadRgb32f = 3, kPayloadRgba32f = 4, kPayloadDisplayRgba8 = 8 };
+
+inline bool payload_format_valid(uint32_t f) { return f == kPayloadRgb32f || f == kPayloadRgba32f || f == kPayloadDisplayRgba8; }
+/* bytes per pixel: 3 or 4 floats, or 4 bytes; format 0 (no output) holds none */
+inline uint64_t payload_pixel_bytes(uint32_t format) { return format == kPayloadDisplayRgba8 ? 4u : 4ull * format; }
+
 /* ---- a frame's rows split among n ranks (wcpt_row_block, wcpt_row_stripes; n > 0, rank < n) ------------------------- */
 
 /* rank r of n holds rows [r * height / n, (r + 1) * height / n): blocks differ by at most one row */

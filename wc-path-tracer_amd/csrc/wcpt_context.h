@@ -24,6 +24,9 @@
 /* wcpt::rt is the runtime's own: none of it, nor a template instantiated over its types, is exported from the library */
 #define WCPT_INTERNAL __attribute__((visibility("hidden")))
 
+static_assert(wcpt::kPayloadRgb32f == WCPT_PAYLOAD_RGB32F && wcpt::kPayloadRgba32f == WCPT_PAYLOAD_RGBA32F &&
+                  wcpt::kPayloadDisplayRgba8 == WCPT_PAYLOAD_DISPLAY_RGBA8, "screen_layout.h PayloadFormat");
+
 namespace wcpt {
 namespace rt WCPT_INTERNAL {
 

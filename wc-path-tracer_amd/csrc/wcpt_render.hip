@@ -12,9 +12,6 @@ using namespace wcpt::rt;
 
 namespace {
 
-/* Bytes per pixel of a gather payload format (wcpt.h WCPT_PAYLOAD_*) */
-uint64_t payload_pixel_bytes(uint32_t format) { return format == WCPT_PAYLOAD_DISPLAY_RGBA8 ? 4u : 4ull * format; }
-
 /* ---- frame preparation: what it decides is stated in frame_prep.h; what it does to the device is below ---------------- */
 
 /* One copy of a draw's primary-ray records (`copy` of the bytes at `dst`) brought to the camera position `origin` (bit
@@ -319,10 +316,10 @@ int check_render_args(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t 
     /* the output's rows: the context's rows back to back, or (WCPT_OPTION_GATHER_FRAME_ROWS) frame rows up to its last */
     const uint64_t wire_rows = ctx->gather_frame_rows ? wcpt::layout_last_row(ctx->layout) + 1u : ctx->layout.rows;
     if (ctx->wire && mode == wcpt::kModeRender &&
-        (uint64_t)ctx->layout.width * wire_rows * payload_pixel_bytes(ctx->wire_ch) > ctx->wire_bytes)
+        (uint64_t)ctx->layout.width * wire_rows * wcpt::payload_pixel_bytes(ctx->wire_ch) > ctx->wire_bytes)
         return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "gather output of %llu bytes too small for %ux%llu x %u B",
                          (unsigned long long)ctx->wire_bytes, ctx->layout.width, (unsigned long long)wire_rows,
-                         (unsigned)payload_pixel_bytes(ctx->wire_ch));
+                         (unsigned)wcpt::payload_pixel_bytes(ctx->wire_ch));
     return WCPT_SUCCESS;
 }
 

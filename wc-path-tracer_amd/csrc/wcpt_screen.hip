@@ -169,7 +169,7 @@ int wcpt_set_gather_output(wcpt_context* ctx, uint64_t device_ptr, uint64_t byte
         ctx->wire_bytes = 0;
         return WCPT_SUCCESS;
     }
-    if (channels != WCPT_PAYLOAD_RGB32F && channels != WCPT_PAYLOAD_RGBA32F && channels != WCPT_PAYLOAD_DISPLAY_RGBA8)
+    if (!wcpt::payload_format_valid(channels))
         return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "gather output format %u (3, 4 or 8)", channels);
     if (bytes == 0 || (device_ptr & 3u))
         return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "gather output: %llu bytes at a misaligned or empty buffer",
