@@ -100,6 +100,8 @@ int main(int argc, char** argv)
     /* ---- frames: editor.jai:149-158 --------------------------------------------------------------------- */
     uint32_t renderedFramesCount = 0;
     wcpt_camera cam = sc.camera;
+    wcpt_scene_data last_sd;
+    memset(&last_sd, 0, sizeof(last_sd));
     for (int f = 0; f < frames; f++) {
         const int moved = (f == move_at);
         if (moved) {
@@ -128,6 +130,16 @@ int main(int argc, char** argv)
         renderedFramesCount += 1;                                            /* :423 */
         printf("frame %d renderedFramesCount %u %s %.3f ms\n", f, sd.renderedFramesCount, moved ? "(moved)" : "",
                t1 - t0);
+        last_sd = sd;
+    }
+
+    /* ---- a click on the viewport's centre (editor.jai:187-188, selectedSphere): what that pixel shows ------------- */
+    if (frames > 0) {
+        static const char* const kinds[] = {"miss", "sphere", "triangle", "?"};
+        wcpt_primary_hit hit;
+        CHECK(ctx, wcpt_pick(ctx, &last_sd, a_sph, a_draw, W / 2u, H / 2u, &hit));
+        printf("pick (%u, %u): %s index %u draw %u t %g%s\n", W / 2u, H / 2u, kinds[hit.kind & WCPT_HIT_KIND_MASK], hit.index,
+               hit.draw, (double)hit.t, (hit.kind & WCPT_HIT_FRONT) ? " (front)" : "");
     }
 
     /* ---- display: composite.comp -> RGBA8 -> PPM ---------------------------------------------------------- */

@@ -42,7 +42,7 @@ extern "C" {
  *    wcpt_group_info gained issue_threads; wcpt_group_set_output reads `bytes` in every process. Later additions that
  *    keep the layouts and calls (no version step): WCPT_GROUP_TRANSPORT_DIRECT, WCPT_OPTION_PROFILE_REGION,
  *    WCPT_OPTION_WF_FETCH, WCPT_OPTION_WF_PIPES 0 (automatic, now the default), wcpt_bvh_refit,
- *    wcpt_bvh_refit_device, wcpt_wf_last_plan. */
+ *    wcpt_bvh_refit_device, wcpt_wf_last_plan, wcpt_trace_primary, wcpt_pick. */
 #define WCPT_ABI_VERSION 4
 
 /* ---- error codes (VkResult-compatible where a VkResult exists) ---------------------------------- */
@@ -129,7 +129,8 @@ extern "C" {
  * 1 two events for the whole profiled region, one before its first render and one recorded by wcpt_profile_end, so
  * kernel_ms_total spans the renders' launches and the gaps between them, and launches counts the renders. Each event
  * record is a packet on the stream: per-render pairs cost ~1.3 % of a 0.36-ms frame (c2: 0.3651-0.3660 against
- * 0.3607-0.3611 ms per frame without, profiles/r05_events_ab.log). Set it outside a profiled region. */
+ * 0.3607-0.3611 ms per frame without, profiles/r05_events_ab.log). Set it outside a profiled region. With 1 a
+ * wcpt_trace_primary pass counts like a render (with 0 it is not timed). */
 #define WCPT_OPTION_PROFILE_REGION 11
 /* Wavefront trace: fetch rounds per traversal iteration. 1: the child pair of an interior lane and the triangle of a
  * leaf lane are fetched together (a lane that descends into a leaf tests it the next iteration); 0: the leaf fetch
@@ -544,6 +545,50 @@ int      wcpt_wf_last_plan(wcpt_context* ctx, wcpt_wf_plan_info* out);
  * Does not write the image. Synchronous. */
 int      wcpt_render_counters(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t materials,
                               uint64_t spheres, uint64_t draw_commands, wcpt_counters* out);
+
+/* ---- what a pixel shows: the primary-hit buffer and the pick. Added under ABI 4. ------------------------ */
+/* One record per pixel: what the reference's Intersect (pathTracer.comp:135-211) leaves in its record for the pixel's
+ * primary ray, in exact arithmetic, with the identity of the primitive. The spheres are tested in index order, then the
+ * draw commands in order, each by the reference's traversal; a closer hit replaces the record only on strict `<`, so
+ * on equal t the earlier primitive in that order stays. p is not stored: it is origin + t * direction on these bits. Of
+ * `scene` only inverseProjection, inverseView, position, sphereCount and drawCommandCount are read, and no material
+ * buffer is needed. Both calls always run exact, whatever WCPT_OPTION_ARITH says. An editor selects the object under a
+ * click with the pick; the buffer (depth, normal, identity per pixel) is the guide image of an outline or a denoiser. */
+#define WCPT_HIT_MISS     0u
+#define WCPT_HIT_SPHERE   1u
+#define WCPT_HIT_TRIANGLE 2u
+#define WCPT_HIT_KIND_MASK 3u
+#define WCPT_HIT_FRONT    0x80000000u
+typedef struct wcpt_primary_hit {
+    float    direction[3];  /*  0  the pixel's primary ray direction (pathTracer.comp:290-302)                       */
+    float    t;             /* 12  hit distance; the kernels' kInfinity (bits 0x7F7FFFFF) on a miss                  */
+    float    normal[3];     /* 16  as Intersect returns it: flipped towards the ray; zeros on a miss                 */
+    uint32_t kind;          /* 28  WCPT_HIT_* in bits 0-1, bit 31 (WCPT_HIT_FRONT) = front: dot(direction, normal)
+                                   was < 0 before the flip                                                           */
+    uint32_t material;      /* 32  the sphere's material; 0 for a triangle (:175) and for a miss                     */
+    uint32_t index;         /* 36  sphere index, or the triangle's number in its draw's permuted index buffer (index
+                                   position / 3); 0 on a miss                                                        */
+    uint32_t draw;          /* 40  draw command of a triangle hit; 0 otherwise                                       */
+    uint32_t _pad;          /* 44  written as 0                                                                      */
+} wcpt_primary_hit;
+/* The context's rows back to back, [rows][width] records, into caller-owned device memory `dst` (16-byte aligned,
+ * `bytes` >= width * rows * 48); a row range and row stripes are honoured with the row map a render uses. Asynchronous
+ * on the context's stream; like wcpt_composite it first orders the stream behind both frame-overlap pipes. A refused
+ * far-child push (a tree deeper than the traversal stack) sets WCPT_ERROR_STACK_OVERFLOW for the next wcpt_sync, as a
+ * render does.
+ * wcpt_pick is the same kernel on a one-pixel window: (x, y) is any pixel of the frame, whether or not the context holds
+ * its row. Synchronous; fills *out on the host and returns a stack overflow itself.
+ * Neither call touches the accumulation image, the gather output, wcpt_last_kernel, wcpt_last_arith, the primary cache or
+ * its statistics, or the split and tiny-tree counters. Both share a render's frame preparation: a prepared scene is not
+ * prepared again, and the next render's preparation still hits.
+ * WCPT_ERROR_INVALID_ARGUMENT (WCPT_ERROR_NO_SCREEN without a screen), with nothing launched or written: a null scene, a
+ * frame that is not renderable ("Frame sizes"), sphereCount > 0 with null spheres, drawCommandCount > 0 with null draw
+ * commands, a draw command a render refuses, a null, misaligned or too small `dst`, a null `out`, x >= width or
+ * y >= height. */
+int      wcpt_trace_primary(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t spheres,
+                            uint64_t draw_commands, uint64_t dst, uint64_t bytes);
+int      wcpt_pick(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t spheres, uint64_t draw_commands,
+                   uint32_t x, uint32_t y, wcpt_primary_hit* out);
 
 /* Wavefront trace-loop phase timers of the last wcpt_render_counters call with WCPT_OPTION_DIAGNOSTICS set
  * (s_memtime cycles summed over waves): {fetch, leaf, interior, pop, epilogue, waves, iterations, -}. */

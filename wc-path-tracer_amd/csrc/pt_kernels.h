@@ -253,6 +253,22 @@ hipError_t bvh_refit_device(const float* vertices, uint32_t vertex_count, const 
  * are cost-ordered); with 0 a pending overlap is joined first and the frame runs on `stream` */
 hipError_t launch_megakernel(const LaunchArgs& a, int mode, int stack_kind, MkState& mk, hipStream_t stream,
                              int overlap = 0);
+/* The primary-hit pass (pt_primary.hip; the record: primary_hit.h): the window of `width` x `rows` pixels whose first
+ * column is frame column x0 and whose local row ly is frame row frame_row(rm, ly), of a W x H frame, as records
+ * [rows][width] at `dst`. A pixel outside the frame is skipped. Of sd only inverseProjection, inverseView, position,
+ * sphereCount and drawCommandCount are read; tri_records is the frame's table (frame_prep.h). Exact arithmetic. */
+struct PrimaryPass {
+    wcpt_scene_data sd;
+    const wcpt_sphere* spheres;
+    const wcpt_draw_command* draws;
+    const uint64_t* tri_records;
+    void* dst;
+    uint32_t W, H, x0, width, rows;
+    RowMap rm;
+    bool pair_records; /* the leaves read pair records (else single records): the frame plan's choice */
+    uint32_t* status;
+};
+hipError_t launch_primary(const PrimaryPass& p, hipStream_t stream);
 /* sort_rays: sort the ray queue by (direction octant, origin Morton code) before each bounce's trace. */
 /* lds_stack: LDS traversal-stack entries per lane of the trace kernel (10, 16 or 24; render mode only). */
 /* pipes: concurrent pipelines (1..kWfMaxPipes; sorting and diagnostics use 1). */

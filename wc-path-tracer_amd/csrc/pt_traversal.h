@@ -533,6 +533,60 @@ __device__ __forceinline__ Hit intersect(const Ray& ray, const wcpt_scene_data& 
     return hit;
 }
 
+/* The closest hit of intersect without its epilogue, for a caller that needs the winner's identity (pt_primary.hip): the
+ * sphere loop, then every draw in order on the multi-draw loop above -- the same steps in the same order, so rt, prim
+ * (kNoPrim, kSpherePrim | sphere, or a triangle's index position) and primDraw are what intersect hands resolve_hit for
+ * this ray. Exact arithmetic, no counting; `primary` as for leaf_step. `pairs` (kernel-uniform) is the frame plan's record
+ * layout, a run-time switch here: every draw's table entry holds both layouts, both leaf forms give the same (rt, prim)
+ * -- the same tests in the same order -- and the caller is one kernel for every plan. */
+struct ClosestHit { float t; uint32_t prim, draw; };
+template <class Stack>
+__device__ __forceinline__ ClosestHit closest_hit(const Ray& ray, const wcpt_scene_data& sd,
+                                                  const wcpt_sphere* __restrict__ spheres,
+                                                  const wcpt_draw_command* __restrict__ draws,
+                                                  const uint64_t* __restrict__ tri_records, Stack& stk, bool& overflow,
+                                                  bool primary, bool pairs)
+{
+    float rt = kInfinity;
+    uint32_t prim = kNoPrim, primDraw = 0;
+    Counters cnt = {};
+    sphere_loop<kArithExact>(ray, sd.sphereCount, spheres, rt, prim);
+    uint32_t curLeft = 0, curCount = 0;
+    PeelCache pc;
+    pc.tag = kNoPeel;
+    pc.t = bc2(0.0f);
+    RefStack rf;
+    uint32_t d = 0;
+    DrawGeom g;
+    float rt_before = rt;
+    auto start_draw = [&]() {
+        for (; d < sd.drawCommandCount; d++) {
+            g = pairs ? draw_geom<true>(draws, tri_records, d) : draw_geom<false>(draws, tri_records, d);
+            rt_before = rt;
+            if (root_step<false>(ray, g, rt, curLeft, curCount, cnt, rf)) {
+                stk.reset();
+                pc.tag = kNoPeel;
+                return true;
+            }
+        }
+        return false;
+    };
+    bool active = start_draw();
+    while (active) {
+        if (curCount > 0) {
+            if (pairs) leaf_step<false, false, true, false, kArithExact>(ray, g, curLeft, curCount, rt, prim, cnt, primary, pc);
+            else leaf_step<false, false, false, false, kArithExact>(ray, g, curLeft, curCount, rt, prim, cnt, primary, pc);
+        } else if (interior_step<false, false>(ray, g, stk, curLeft, curCount, rt, cnt, overflow, rf)) {
+            continue;
+        }
+        if (pop_step<false>(g, stk, curLeft, curCount, rt, cnt, rf)) continue;
+        if (rt != rt_before) primDraw = d; /* this draw lowered rt: it owns prim */
+        d++;
+        active = start_draw();
+    }
+    return {rt, prim, primDraw};
+}
+
 } // namespace wcpt::dev
 
 #endif /* WCPT_PT_TRAVERSAL_H */

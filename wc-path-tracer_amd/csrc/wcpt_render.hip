@@ -1,11 +1,13 @@
 /*
  * wcpt_render.hip — C-ABI runtime, a frame: its preparation (the triangle records of every draw command, their table,
- * what the frame runs), the render dispatch with its counting and diagnostics runs, the validation a group makes of
- * all its ranks first, and the device self-tests. render_common and everything it calls per frame are here.
+ * what the frame runs), the render dispatch with its counting and diagnostics runs, the primary-hit pass and the pick
+ * (which share that preparation), the validation a group makes of all its ranks first, and the device self-tests.
+ * render_common and everything it calls per frame are here.
  */
 #include <algorithm>
 #include <cstddef>
 
+#include "primary_hit.h"
 #include "wcpt_context.h"
 
 using namespace wcpt::rt;
@@ -323,6 +325,30 @@ int check_render_args(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t 
     return WCPT_SUCCESS;
 }
 
+/* Profiling events time the launches only: no system-scope fence when they are recorded (hip_runtime_api.h,
+ * hipEventDisableSystemFence), so the timed frames pay no cache writeback between launches (c2 0.538 -> 0.534
+ * ms/frame against hipEventReleaseToDevice and hipEventDefault, which measured alike). */
+#ifndef WCPT_PROFILE_EVENT_FLAGS
+#define WCPT_PROFILE_EVENT_FLAGS hipEventDisableSystemFence
+#endif
+
+/* Region timing (WCPT_OPTION_PROFILE_REGION) of a render or a primary-hit pass about to be queued: one event before the
+ * first launch since wcpt_profile_begin; wcpt_profile_end records the closing one. */
+int region_launch(wcpt_context* ctx)
+{
+    if (ctx->events.empty()) {
+        hipEvent_t b, c;
+        HIP_TRY(ctx, hipEventCreateWithFlags(&b, WCPT_PROFILE_EVENT_FLAGS), "hipEventCreate");
+        HIP_TRY(ctx, hipEventCreateWithFlags(&c, WCPT_PROFILE_EVENT_FLAGS), "hipEventCreate");
+        ctx->events.emplace_back(b, c);
+    }
+    if (ctx->region_renders++ == 0) {
+        HIP_TRY(ctx, hipEventRecord(ctx->events[0].first, ctx->stream), "hipEventRecord");
+        ctx->events_used = 1;
+    }
+    return WCPT_SUCCESS;
+}
+
 int render_common(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t materials, uint64_t spheres,
                   uint64_t draws, int mode)
 {
@@ -369,24 +395,9 @@ int render_common(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t mate
     a.wf_persist = ctx->wf_persist;
     a.mk_tile_order = (uint32_t)ctx->mk_tile_order;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-/* Profiling events time the launches only: no system-scope fence when they are recorded (hip_runtime_api.h,
- * hipEventDisableSystemFence), so the timed frames pay no cache writeback between launches (c2 0.538 -> 0.534
- * ms/frame against hipEventReleaseToDevice and hipEventDefault, which measured alike). */
-#ifndef WCPT_PROFILE_EVENT_FLAGS
-#define WCPT_PROFILE_EVENT_FLAGS hipEventDisableSystemFence
-#endif
     if (ctx->profiling && mode == wcpt::kModeRender && ctx->profile_region) {
-        /* region timing: one event before the first render; wcpt_profile_end records the closing one */
-        if (ctx->events.empty()) {
-            hipEvent_t b, c;
-            HIP_TRY(ctx, hipEventCreateWithFlags(&b, WCPT_PROFILE_EVENT_FLAGS), "hipEventCreate");
-            HIP_TRY(ctx, hipEventCreateWithFlags(&c, WCPT_PROFILE_EVENT_FLAGS), "hipEventCreate");
-            ctx->events.emplace_back(b, c);
-        }
-        if (ctx->region_renders++ == 0) {
-            HIP_TRY(ctx, hipEventRecord(ctx->events[0].first, ctx->stream), "hipEventRecord");
-            ctx->events_used = 1;
-        }
+        rc = region_launch(ctx);
+        if (rc) return rc;
     } else if (ctx->profiling && mode == wcpt::kModeRender) {
         if (ctx->events_used == ctx->events.size()) {
             hipEvent_t b, c;
@@ -444,11 +455,63 @@ int render_common(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t mate
     return WCPT_SUCCESS;
 }
 
-/* the self-tests' scratch: their inputs, then their outputs */
+/* the self-tests' scratch (their inputs, then their outputs) and the pick's one record */
 int ensure_scratch(wcpt_context* ctx, uint64_t bytes)
 {
     if (ctx->scratch_bytes >= bytes) return WCPT_SUCCESS;
     return grow(ctx, ctx->d_scratch, ctx->scratch_bytes, bytes, bytes, "hipMalloc(selftest scratch)");
+}
+
+/* ---- the primary-hit pass (pt_primary.hip, primary_hit.h) -------------------------------------------------------------- */
+
+/* What wcpt_trace_primary and wcpt_pick (`who`) refuse about the scene and the screen before any device work: a render's
+ * checks without the material buffer and the gather output. */
+int check_primary_args(wcpt_context* ctx, const char* who, const wcpt_scene_data* scene, uint64_t spheres, uint64_t draws)
+{
+    if (!scene) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "%s: null SceneData", who);
+    if (ctx->layout.width == 0 || ctx->layout.height == 0 || ctx->layout.rows == 0)
+        return set_error(ctx, WCPT_ERROR_NO_SCREEN, "%s: no screen (call wcpt_create_screen)", who);
+    if (!wcpt::layout_renderable(ctx->layout))
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "%s: the context's %u rows of width %u cover %llu 8x8 tiles, more "
+                         "than 2^26 - 1", who, ctx->layout.rows, ctx->layout.width,
+                         (unsigned long long)wcpt::layout_tiles(ctx->layout));
+    if (scene->sphereCount > 0 && spheres == 0)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "%s: sphereCount > 0 with a null sphere buffer", who);
+    if (scene->drawCommandCount > 0 && draws == 0)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "%s: drawCommandCount > 0 with null draw commands", who);
+    return WCPT_SUCCESS;
+}
+
+/* The pass over one window (PrimaryPass: x0, width, rows, rm, dst), behind both frame-overlap pipes and a render's frame
+ * preparation, which it shares: a prepared scene is not prepared again and the next render's preparation still hits. The
+ * plan the preparation makes is a render's business: what the last render ran (wcpt_last_kernel) stays. `timed`: the pass
+ * counts in a profiled region (WCPT_OPTION_PROFILE_REGION). */
+int primary_pass(wcpt_context* ctx, const wcpt_scene_data& scene, uint64_t spheres, uint64_t draws, wcpt::PrimaryPass& p,
+                 bool timed)
+{
+    int rc = join_pending(ctx);
+    if (rc) return rc;
+    wcpt::LaunchArgs a;
+    a.tri_records = nullptr;
+    const int kernel_run = ctx->kernel_run;
+    rc = prepare_tri_records(ctx, scene, draws, a);
+    ctx->kernel_run = kernel_run;
+    if (rc) return rc;
+    p.sd = scene;
+    p.spheres = reinterpret_cast<const wcpt_sphere*>(spheres);
+    p.draws = reinterpret_cast<const wcpt_draw_command*>(draws);
+    p.tri_records = a.tri_records;
+    p.pair_records = a.pair_records;
+    p.W = ctx->layout.width;
+    p.H = ctx->layout.height;
+    p.status = ctx->d_status;
+    /* region timing counts the pass once nothing can refuse it any more: a pass the preparation refused was no launch */
+    if (timed && ctx->profiling && ctx->profile_region) {
+        rc = region_launch(ctx);
+        if (rc) return rc;
+    }
+    HIP_TRY(ctx, wcpt::launch_primary(p, ctx->stream), "primary-hit launch");
+    return WCPT_SUCCESS;
 }
 
 } // namespace
@@ -527,6 +590,57 @@ int wcpt_render_counters(wcpt_context* ctx, const wcpt_scene_data* scene, uint64
     std::memcpy(out, h, sizeof(h));
     if (h[15] == 0xFFFFFFFFull) out->ref_stack_max = UINT64_MAX;
     return read_status(ctx);
+}
+
+/* ---- the primary-hit buffer and the pick ---------------------------------------------------------- */
+int wcpt_trace_primary(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t spheres, uint64_t draw_commands,
+                       uint64_t dst, uint64_t bytes)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    rc = check_primary_args(ctx, "wcpt_trace_primary", scene, spheres, draw_commands);
+    if (rc) return rc;
+    const uint64_t need = wcpt::primary_hit_bytes(ctx->layout.width, ctx->layout.rows);
+    if (dst == 0 || dst % 16u != 0)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "wcpt_trace_primary: output address 0x%llx (16-byte aligned, not null)",
+                         (unsigned long long)dst);
+    if (bytes < need)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "wcpt_trace_primary: output of %llu bytes too small for %ux%u x %u B",
+                         (unsigned long long)bytes, ctx->layout.width, ctx->layout.rows, wcpt::kPrimHitBytes);
+    wcpt::PrimaryPass p;
+    p.dst = reinterpret_cast<void*>(dst);
+    p.x0 = 0;
+    p.width = ctx->layout.width;
+    p.rows = ctx->layout.rows;
+    p.rm = wcpt::layout_row_map(ctx->layout);
+    return primary_pass(ctx, *scene, spheres, draw_commands, p, true);
+}
+
+int wcpt_pick(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t spheres, uint64_t draw_commands, uint32_t x,
+              uint32_t y, wcpt_primary_hit* out)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    rc = check_primary_args(ctx, "wcpt_pick", scene, spheres, draw_commands);
+    if (rc) return rc;
+    if (!out) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "wcpt_pick: null output");
+    if (x >= ctx->layout.width || y >= ctx->layout.height)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "wcpt_pick: pixel (%u, %u) outside the %ux%u frame", x, y,
+                         ctx->layout.width, ctx->layout.height);
+    rc = ensure_scratch(ctx, wcpt::kPrimHitBytes);
+    if (rc) return rc;
+    /* the one-pixel window at (x, y): a block of one row from frame row y, whichever rows the context holds */
+    wcpt::PrimaryPass p;
+    p.dst = ctx->d_scratch;
+    p.x0 = x;
+    p.width = 1;
+    p.rows = 1;
+    p.rm = wcpt::RowMap{y, wcpt::kContiguousShift, 0u};
+    rc = primary_pass(ctx, *scene, spheres, draw_commands, p, false); /* a pick is not a timed pass */
+    if (rc) return rc;
+    static_assert(sizeof(wcpt_primary_hit) == wcpt::kPrimHitBytes, "wcpt_primary_hit is primary_hit.h's record");
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_scratch, sizeof(*out), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync(pick)");
+    return read_status(ctx); /* synchronises: *out is filled */
 }
 
 int wcpt_read_diagnostics(wcpt_context* ctx, uint64_t* out, uint32_t n)

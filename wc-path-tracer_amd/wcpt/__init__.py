@@ -5,7 +5,8 @@ package is the Python host mirror used by tests and the benchmark.
 """
 from ._lib import (BloomParams, COUNTER_FIELDS, DRAW_COMMAND_DTYPE, EXPORTED_SYMBOLS, KERNEL_AUTO, KERNEL_MEGAKERNEL,
                    KERNEL_WAVEFRONT, LIB_PATH, MATERIAL_DIELECTRIC, MATERIAL_DTYPE, MATERIAL_METAL, NODE_DTYPE,
-                   SCENE_DATA_DTYPE, SPHERE_DTYPE, Camera, WcptError, lib)
+                   SCENE_DATA_DTYPE, SPHERE_DTYPE, PRIMARY_HIT_DTYPE, HIT_MISS, HIT_SPHERE, HIT_TRIANGLE, HIT_KIND_MASK,
+                   HIT_FRONT, Camera, WcptError, lib)
 from .renderer import Context, DeviceScene, Editor, Group, PathTracingRenderer, group_unique_id
 from . import scene
 from . import _lib
@@ -16,6 +17,7 @@ __all__ = [
     "SCENE_DATA_DTYPE", "SPHERE_DTYPE", "Camera", "WcptError", "lib", "Context", "DeviceScene",
     "PathTracingRenderer", "Editor", "Group", "group_unique_id", "scene", "device_count", "device_pci_bus_id", "runtime_version", "build_id",
     "BloomParams", "bloom_levels", "bloom_host",
+    "PRIMARY_HIT_DTYPE", "HIT_MISS", "HIT_SPHERE", "HIT_TRIANGLE", "HIT_KIND_MASK", "HIT_FRONT",
 ]
 
 

@@ -85,6 +85,15 @@ NODE_DTYPE = np.dtype([("min", "<f4", (3,)), ("max", "<f4", (3,)), ("leftNodeOrT
                        ("triangleCount", "<u4")])
 DRAW_COMMAND_DTYPE = np.dtype([("vertexBuffer", "<u8"), ("indexBuffer", "<u8"), ("bvhBuffer", "<u8"),
                                ("indexCount", "<u4"), ("_pad", "<u4")])
+# wcpt_primary_hit (wcpt_trace_primary, wcpt_pick; csrc/primary_hit.h): 48 bytes, three 16-byte rows
+PRIMARY_HIT_DTYPE = np.dtype([("direction", "<f4", (3,)), ("t", "<f4"), ("normal", "<f4", (3,)), ("kind", "<u4"),
+                              ("material", "<u4"), ("index", "<u4"), ("draw", "<u4"), ("_pad", "<u4")])
+HIT_MISS = 0
+HIT_SPHERE = 1
+HIT_TRIANGLE = 2
+HIT_KIND_MASK = 3        # `kind` bits 0-1
+HIT_FRONT = 0x80000000   # `kind` bit 31: the ray met the surface from its front
+assert PRIMARY_HIT_DTYPE.itemsize == 48
 WORK_FIELDS = ("pixels", "segments", "sphere_tests", "node_pops", "interior_visits", "triangle_tests",
                "hits", "draw_fetches")
 DIAG_FIELDS = ("wave_interior_steps", "lane_interior_steps", "wave_triangle_steps", "lane_triangle_steps",
@@ -226,6 +235,8 @@ _PROTOTYPES = {
     "wcpt_mk_tiny_tree_stats": (_i, [_p, C.POINTER(_u64)]),
     "wcpt_wf_last_plan": (_i, [_p, C.POINTER(WfPlanInfo)]),
     "wcpt_render_counters": (_i, [_p, _p, _u64, _u64, _u64, C.POINTER(Counters)]),
+    "wcpt_trace_primary": (_i, [_p, _p, _u64, _u64, _u64, _u64]),
+    "wcpt_pick": (_i, [_p, _p, _u64, _u64, _u32, _u32, _p]),
     "wcpt_read_diagnostics": (_i, [_p, C.POINTER(C.c_uint64), _u32]),
     "wcpt_profile_begin": (_i, [_p]),
     "wcpt_profile_end": (_i, [_p, C.POINTER(C.c_double), C.POINTER(_u32)]),

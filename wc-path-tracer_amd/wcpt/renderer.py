@@ -13,7 +13,7 @@ import numpy as np
 
 from ._lib import (COUNTER_FIELDS, DRAW_COMMAND_DTYPE, GROUP_OPTION_ROW_STRIPE, GROUP_TRANSPORT_RCCL,
                    GROUP_UNIQUE_ID_BYTES, ARITH_EXACT, OPTION_ARITH, OPTION_DIAGNOSTICS,
-                   MATERIAL_DTYPE, NODE_DTYPE, SCENE_DATA_DTYPE, SPHERE_DTYPE, Camera, Counters, GroupInfo, WcptError, WfPlanInfo, check, lib, ptr)
+                   HIT_KIND_MASK, HIT_SPHERE, MATERIAL_DTYPE, NODE_DTYPE, PRIMARY_HIT_DTYPE, SCENE_DATA_DTYPE, SPHERE_DTYPE, Camera, Counters, GroupInfo, WcptError, WfPlanInfo, check, lib, ptr)
 from . import scene as _scene
 
 
@@ -184,6 +184,38 @@ class Context:
 
     def sync(self):
         self._chk(lib.wcpt_sync(self.h))
+
+    def trace_primary(self, sd: np.ndarray, spheres: int, draws: int, dst: int | None = None, nbytes: int | None = None,
+                      rows: int | None = None):
+        """wcpt_trace_primary: the primary hit of every pixel of the context's rows (PRIMARY_HIT_DTYPE: depth, normal
+        and the identity of the sphere or triangle). With a device address `dst` (16-byte aligned) the pass is only
+        queued; `nbytes` is then the size of the caller's memory at `dst`, which the library checks against width * rows
+        * 48 -- the wrapper does not make it up. With dst=None it runs into a buffer of the context's, is waited for, and
+        the records come back as a structured array [rows, width]; `rows` are the rows the context holds (default the
+        whole frame: like readback, the wrapper does not track a row range or stripes)."""
+        sd = np.ascontiguousarray(sd, dtype=SCENE_DATA_DTYPE)
+        if dst is not None:
+            if nbytes is None:
+                raise ValueError("trace_primary: with a device address, pass the size of its memory as nbytes")
+            self._chk(lib.wcpt_trace_primary(self.h, ptr(sd), spheres, draws, dst, nbytes))
+            return None
+        rows = self.height if rows is None else rows
+        nbytes = rows * self.width * PRIMARY_HIT_DTYPE.itemsize
+        buf = self.buffer_alloc(nbytes)
+        try:
+            self._chk(lib.wcpt_trace_primary(self.h, ptr(sd), spheres, draws, self.buffer_address(buf), nbytes))
+            self.sync()
+            out = np.frombuffer(self.buffer_download(buf, nbytes), PRIMARY_HIT_DTYPE)
+        finally:
+            self.buffer_free(buf)
+        return out.reshape(rows, self.width).copy()
+
+    def pick(self, sd: np.ndarray, spheres: int, draws: int, x: int, y: int) -> np.ndarray:
+        """wcpt_pick: the primary hit of frame pixel (x, y), a one-element PRIMARY_HIT_DTYPE array. Synchronous."""
+        sd = np.ascontiguousarray(sd, dtype=SCENE_DATA_DTYPE)
+        out = np.zeros(1, PRIMARY_HIT_DTYPE)
+        self._chk(lib.wcpt_pick(self.h, ptr(sd), spheres, draws, x, y, ptr(out)))
+        return out
 
     def primary_cache_stats(self) -> tuple:
         """(writes, reads): the renders that stored / read the primary cache (WCPT_OPTION_PRIMARY_CACHE)."""
@@ -531,6 +563,17 @@ class PathTracingRenderer:
     def Readback(self) -> np.ndarray:
         return self.ctx.readback()
 
+    def Pick(self, camera: Camera, x: int, y: int):
+        """What pixel (x, y) of the frame shows from `camera` (wcpt_pick): (record, position) -- the PRIMARY_HIT_DTYPE
+        record of the pixel's primary ray and the hit point origin + t * direction in float32 (of no meaning on a miss).
+        The frame counter and the accumulation are left alone."""
+        sd = self.scene_data(camera)
+        rec = self.ctx.pick(sd, self.ctx.buffer_address(self._sph_buf), self.ctx.buffer_address(self._draw_buf), x, y)[0]
+        origin = np.asarray(sd["position"], np.float32)
+        with np.errstate(over="ignore", invalid="ignore"):
+            position = origin + np.float32(rec["t"]) * np.asarray(rec["direction"], np.float32)
+        return rec, position
+
     # Deinit :473-490
     def Deinit(self):
         for b in self._mesh_bufs:
@@ -558,6 +601,19 @@ class Editor:
     def __init__(self, renderer: PathTracingRenderer, camera: Camera):
         self.renderer = renderer
         self.camera = camera
+        self.selectedSphere = -1     # editor.jai: the selected sphere's index, -1 = nothing selected
+
+    def select(self, x: int, y: int):
+        """A click on pixel (x, y) of the viewport: ``selectedSphere`` becomes the index of the sphere the pixel shows,
+        or -1 when it shows the mesh or the sky. Returns the pixel's record (PathTracingRenderer.Pick); no frame counter
+        changes, so the accumulation goes on."""
+        r = self.renderer
+        w, h = r.renderSize
+        cam = _scene.update_camera(self.camera, w / h)
+        rec, _ = r.Pick(cam, x, y)
+        is_sphere = (int(rec["kind"]) & HIT_KIND_MASK) == HIT_SPHERE
+        self.selectedSphere = int(rec["index"]) if is_sphere else -1
+        return rec
 
     def frame(self, moved: bool = False) -> int:
         r = self.renderer
