@@ -17,10 +17,17 @@
  * log/cos/exp are the deterministic definitions of wc-path-tracer_amd/csrc/wcpt_libm.h (GLSL leaves their
  * precision to the driver; see DESIGN.md "Parity").
  *
- * Parity pinning: the reference cannot be built or run here (Jai host, GLSL needing glslc + a Vulkan ICD;
- * SURVEY.md §8(c)). The RNG is pinned by the known-answer values of SURVEY.md §4 (tests/test_oracle.py);
- * the intersection primitives by hand-derived known answers; full images are "parity unpinned" against
- * reference execution and are pinned as committed golden fixtures of this oracle (tests/golden/).
+ * Parity pinning: the reference's host cannot be built or run here (Jai; a Vulkan ICD), but its
+ * shader text can be executed: oracle/ref_translate.py rewrites pathTracer.comp, composite.comp and bloom.comp
+ * mechanically, oracle/ref_driver.cpp compiles them for the CPU behind oracle/glsl_cpu.hpp (GLSL's types and built-ins
+ * from the specification's formulas, the latitude it leaves taken as listed above and in that header's table), and
+ * tests/test_reference_shader.py, test_reference_functions.py and test_reference_display.py hold this file to the
+ * result bit for bit: full images (the golden fixtures of tests/golden/ among them), the intersection functions, the
+ * RNG, CalculateReflectance, and oracle_composite. So control flow, operand order, which rand() is drawn and every
+ * constant are pinned to executed reference text. What stays unpinned: the built-ins' latitude (a driver's log, cos,
+ * exp, pow, division and sampler may round otherwise), cases deeper than the reference's nodeStack[32], and the Jai
+ * host code restated below and in wc-path-tracer_amd/host/ (the BVH builder, the OBJ loader, the camera), which is
+ * pinned only by the known answers of SURVEY.md §4 and the asset counts (tests/test_oracle.py, tests/test_host.py).
  *
  * Instrumented with the per-frame counters of SURVEY.md §8(d) (wcpt_counters).
  */
