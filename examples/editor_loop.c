@@ -7,6 +7,8 @@
  *   per frame (editor.jai:149-158)               camera still ? renderedFramesCount += 1 : = 0
  *                                                UpdateMaterials (:459-471) -> Render (:399-457, count += 1)
  *   display (composite.comp)                     gamma + PBR Neutral -> RGBA8 -> PPM file
+ *   denoised display                             the last frame's primary-hit records as the guide (wcpt_trace_primary),
+ *                                                wcpt_composite_denoise -> RGBA8 -> <out>_denoised.ppm beside it
  *
  *   usage: editor_loop [scene=cornell] [width=640] [height=360] [frames=8] [out.ppm] [--move-at K]
  *
@@ -47,6 +49,23 @@ static int upload(wcpt_context* ctx, wcpt_buffer* buf, const void* data, uint64_
     return *addr ? WCPT_SUCCESS : WCPT_ERROR_INVALID_HANDLE;
 }
 
+/* the RGBA8 frame in buffer `buf` as a binary PPM */
+static int write_ppm(wcpt_context* ctx, wcpt_buffer buf, uint32_t W, uint32_t H, const char* path)
+{
+    uint8_t* px = (uint8_t*)malloc((size_t)W * H * 4u);
+    if (!px) return WCPT_ERROR_OUT_OF_HOST_MEMORY;
+    const int rc = wcpt_buffer_download(ctx, buf, px, (uint64_t)W * H * 4u, 0);
+    FILE* fp = rc == WCPT_SUCCESS ? fopen(path, "wb") : NULL;
+    if (fp) {
+        fprintf(fp, "P6\n%u %u\n255\n", W, H);
+        for (uint64_t i = 0; i < (uint64_t)W * H; i++) fwrite(px + 4 * i, 1, 3, fp);
+        fclose(fp);
+        printf("wrote %s\n", path);
+    }
+    free(px);
+    return rc;
+}
+
 int main(int argc, char** argv)
 {
     const char* scene_name = argc > 1 ? argv[1] : "cornell";
@@ -76,7 +95,7 @@ int main(int argc, char** argv)
 
     wcpt_context* ctx = NULL;
     CHECK(NULL, wcpt_create(0, &ctx));
-    wcpt_buffer b_vtx = 0, b_idx = 0, b_bvh = 0, b_draw = 0, b_mat = 0, b_sph = 0, b_out = 0;
+    wcpt_buffer b_vtx = 0, b_idx = 0, b_bvh = 0, b_draw = 0, b_mat = 0, b_sph = 0, b_out = 0, b_guide = 0;
     uint64_t a_vtx = 0, a_idx = 0, a_bvh = 0, a_draw = 0, a_mat = 0, a_sph = 0;
     uint32_t draw_count = 0;
     if (sc.mesh.index_count) {
@@ -145,20 +164,29 @@ int main(int argc, char** argv)
     /* ---- display: composite.comp -> RGBA8 -> PPM ---------------------------------------------------------- */
     CHECK(ctx, wcpt_composite(ctx, wcpt_buffer_device_address(ctx, b_out), WCPT_COMPOSITE_RGBA8));
     CHECK(ctx, wcpt_sync(ctx));
-    uint8_t* px = (uint8_t*)malloc((size_t)W * H * 4u);
-    CHECK(ctx, wcpt_buffer_download(ctx, b_out, px, (uint64_t)W * H * 4u, 0));
-    FILE* fp = fopen(out_path, "wb");
-    if (fp) {
-        fprintf(fp, "P6\n%u %u\n255\n", W, H);
-        for (uint64_t i = 0; i < (uint64_t)W * H; i++) fwrite(px + 4 * i, 1, 3, fp);
-        fclose(fp);
-        printf("wrote %s\n", out_path);
+    CHECK(ctx, write_ppm(ctx, b_out, W, H, out_path));
+
+    /* ---- the same frame denoised: the guide is the primary-hit buffer of the last frame's camera, traced once per
+     * camera move in an editor; the filter runs between the accumulation image and the display step ------------- */
+    if (frames > 0) {
+        const uint64_t guide_bytes = (uint64_t)W * H * sizeof(wcpt_primary_hit);
+        const wcpt_denoise_params dn = {5, 4.0f, 0.5f, 0.05f}; /* the callers' defaults */
+        char path[1024];
+        const char* dot = strrchr(out_path, '.');
+        const int stem = dot ? (int)(dot - out_path) : (int)strlen(out_path);
+        snprintf(path, sizeof(path), "%.*s_denoised%s", stem, out_path, dot ? dot : "");
+        CHECK(ctx, wcpt_buffer_alloc(ctx, guide_bytes, &b_guide));
+        const uint64_t a_guide = wcpt_buffer_device_address(ctx, b_guide);
+        CHECK(ctx, wcpt_trace_primary(ctx, &last_sd, a_sph, a_draw, a_guide, guide_bytes));
+        CHECK(ctx, wcpt_composite_denoise(ctx, a_guide, guide_bytes, wcpt_buffer_device_address(ctx, b_out),
+                                          WCPT_COMPOSITE_RGBA8, &dn));
+        CHECK(ctx, wcpt_sync(ctx));
+        CHECK(ctx, write_ppm(ctx, b_out, W, H, path));
     }
 
     /* ---- Deinit (:473-490) -------------------------------------------------------------------------------- */
-    free(px);
     free(nodes);
-    wcpt_buffer bufs[] = {b_vtx, b_idx, b_bvh, b_draw, b_mat, b_sph, b_out};
+    wcpt_buffer bufs[] = {b_vtx, b_idx, b_bvh, b_draw, b_mat, b_sph, b_out, b_guide};
     for (size_t i = 0; i < sizeof(bufs) / sizeof(bufs[0]); i++)
         if (bufs[i]) wcpt_buffer_free(ctx, bufs[i]);
     wcpt_destroy(ctx);

@@ -553,7 +553,8 @@ int      wcpt_render_counters(wcpt_context* ctx, const wcpt_scene_data* scene, u
  * on equal t the earlier primitive in that order stays. p is not stored: it is origin + t * direction on these bits. Of
  * `scene` only inverseProjection, inverseView, position, sphereCount and drawCommandCount are read, and no material
  * buffer is needed. Both calls always run exact, whatever WCPT_OPTION_ARITH says. An editor selects the object under a
- * click with the pick; the buffer (depth, normal, identity per pixel) is the guide image of an outline or a denoiser. */
+ * click with the pick; the buffer (depth, normal, identity per pixel) is the guide image of an outline or of the
+ * denoiser below (wcpt_composite_denoise). */
 #define WCPT_HIT_MISS     0u
 #define WCPT_HIT_SPHERE   1u
 #define WCPT_HIT_TRIANGLE 2u
@@ -589,6 +590,45 @@ int      wcpt_trace_primary(wcpt_context* ctx, const wcpt_scene_data* scene, uin
                             uint64_t draw_commands, uint64_t dst, uint64_t bytes);
 int      wcpt_pick(wcpt_context* ctx, const wcpt_scene_data* scene, uint64_t spheres, uint64_t draw_commands,
                    uint32_t x, uint32_t y, wcpt_primary_hit* out);
+
+/* ---- guided denoise for the display step. Added under ABI 4. -------------------------------------------------- */
+/* An interactive session is mostly one-sample frames (the reference's editor restarts the accumulation on every camera
+ * move and gizmo drag). wcpt_composite_denoise is wcpt_composite with an edge-avoiding a-trous wavelet filter (Dammertz
+ * et al. 2010) between the accumulation image and the display step, guided by the primary-hit records: `iterations`
+ * passes of a 5x5 B3-spline kernel whose taps lie 1, 2, 4, ... pixels apart; a tap counts only when it shows the same
+ * surface as the pixel -- the same sphere, the same draw command, or the sky -- and is weighted down by its colour
+ * difference (sigma_color), its normal difference (sigma_normal) and its distance from the pixel's tangent plane relative
+ * to the pixel's hit distance (sigma_depth). The reference has no textures, so a surface's albedo is constant and the
+ * identity test does what albedo demodulation does elsewhere. The reference has no denoiser: csrc/wcpt_denoise.h fixes the
+ * rule and the order of every operation; DESIGN.md section 8 has what it is worth. Callers' defaults: 5, 4.0, 0.5, 0.05. */
+typedef struct wcpt_denoise_params {
+    uint32_t iterations;   /* 1..6 */
+    float    sigma_color;  /* > 0, not NaN; +inf turns the colour term off */
+    float    sigma_normal; /* finite, > 0 */
+    float    sigma_depth;  /* finite, > 0: relative to the pixel's hit distance */
+} wcpt_denoise_params;
+/* `guide` is caller-owned device memory (16-byte aligned, `guide_bytes` >= width * height * 48) holding the
+ * [height][width] records wcpt_trace_primary wrote for the camera and scene of the accumulated frames; the call traces
+ * nothing and needs no scene. Asynchronous on the context's stream, same `dst` and `format` as wcpt_composite. Like
+ * wcpt_composite it first orders the stream behind both frame-overlap pipes; it reads the accumulation image and never
+ * writes it, leaves the primary cache, the frame preparation, wcpt_last_kernel, wcpt_last_arith and every counter alone,
+ * and always runs exact. Its scratch (64 bytes per pixel) is the context's: allocated by the first call, grown on a
+ * larger screen, freed by wcpt_destroy. A guide that does not belong to the image gives a wrong picture but never an
+ * access outside the two buffers: guide contents are only compared and multiplied, never used as an index.
+ * WCPT_ERROR_NO_SCREEN without a screen. WCPT_ERROR_INVALID_ARGUMENT, with nothing launched or written: a null `p`,
+ * iterations outside 1..6, a sigma that is NaN, <= 0 or (except sigma_color) infinite, a null guide, one that is not
+ * 16-byte aligned, guide_bytes below width * height * 48, a guide inside a context buffer too small for that, what
+ * wcpt_composite refuses about `dst` and `format`, and a context that does not hold the whole frame (wcpt_set_row_range
+ * or wcpt_set_row_stripes in effect): the filter reads neighbouring rows, as bloom does. Not provided: denoise and bloom
+ * in one call, halos for row blocks, a denoised group payload (WCPT_PAYLOAD_DISPLAY_RGBA8). */
+int      wcpt_composite_denoise(wcpt_context* ctx, uint64_t guide, uint64_t guide_bytes, uint64_t dst, int format,
+                                const wcpt_denoise_params* p);
+/* The same result computed on the CPU by the same arithmetic (csrc/wcpt_denoise.h) from a float4 image and the records
+ * of width x height pixels: RGBA32F into `out_rgba32f` and RGBA8 into `out_rgba8`; either may be NULL. No GPU needed.
+ * Refuses as wcpt_composite_denoise does about `p` (and a null image, a null guide, a frame without pixels), writing
+ * nothing. */
+int      wcpt_denoise_host(const float* rgba, const wcpt_primary_hit* guide, uint32_t width, uint32_t height,
+                           const wcpt_denoise_params* p, float* out_rgba32f, uint8_t* out_rgba8);
 
 /* Wavefront trace-loop phase timers of the last wcpt_render_counters call with WCPT_OPTION_DIAGNOSTICS set
  * (s_memtime cycles summed over waves): {fetch, leaf, interior, pop, epilogue, waves, iterations, -}. */

@@ -221,6 +221,14 @@ uint64_t bloom_pyramid_texels(uint32_t levels, const uint32_t* lw, const uint32_
 hipError_t launch_composite_bloom(const float4* img, uint32_t width, uint32_t height, float threshold, float knee,
                                   uint32_t levels, const uint32_t* lw, const uint32_t* lh, float4* down, float4* up, void* dst,
                                   bool rgba8, hipStream_t stream);
+/* The guided a-trous denoise in front of the display step (pt_denoise.hip; the rule of wcpt_denoise.h): the width x
+ * height records at `records` are packed into the guide, `iterations` iterations run from `img` through the two images
+ * of `scratch` (denoise_scratch_bytes bytes), and the last one's result goes through the display step into rgba32f or
+ * RGBA8 at `dst`. 1 + iterations launches; `img` is only read. */
+uint64_t denoise_scratch_bytes(uint32_t width, uint32_t height);
+hipError_t launch_composite_denoise(const float4* img, const void* records, uint32_t width, uint32_t height,
+                                    uint32_t iterations, float sigma_color, float sigma_normal, float sigma_depth,
+                                    void* scratch, void* dst, bool rgba8, hipStream_t stream);
 /* wcpt_bvh_build_device (pt_bvh_build.hip; the rule in bvh_midpoint.h): the midpoint BVH of the triangles
  * indices[0 .. index_count) over `vertices` into `nodes` (2 * index_count / 3 of them) with `indices` permuted, in
  * `scratch` of bvh_build_scratch_bytes(index_count) bytes. Blocks the host: *status is 0 and *nodes_used the node count

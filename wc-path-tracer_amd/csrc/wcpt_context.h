@@ -98,6 +98,8 @@ struct wcpt_context {
     uint32_t* d_scan = nullptr;        /* leaf-count scan flag (prepare_tri_records) */
     float4* d_bloom = nullptr;         /* wcpt_composite_bloom: the down pyramid, then the up pyramid (on first use) */
     uint64_t bloom_bytes = 0;
+    void* d_denoise = nullptr;         /* wcpt_composite_denoise: two float4 images, then the packed guide (on first use) */
+    uint64_t denoise_bytes = 0;
     void* d_bvh = nullptr;             /* wcpt_bvh_build_device / _sah_device / wcpt_bvh_refit_device: their scratch (on first use, grown on demand) */
     uint64_t bvh_bytes = 0;
     void* d_bvh_bins = nullptr;        /* wcpt_bvh_build_sah_device: the bins of a level's open nodes (grown on demand) */

@@ -1,10 +1,12 @@
 /*
  * wcpt_screen.hip — C-ABI runtime, the output image (CreateScreen / Resize): the frame's size and the rows of it the
  * context holds (screen_layout.h states every rule; here are their messages and the device's part), an external image,
- * the gather output, readback and upload, and the display step (wcpt_composite, wcpt_composite_bloom).
+ * the gather output, readback and upload, and the display step (wcpt_composite, wcpt_composite_bloom,
+ * wcpt_composite_denoise).
  */
 #include "wcpt_context.h"
 #include "wcpt_bloom.h"
+#include "wcpt_denoise.h"
 
 using namespace wcpt::rt;
 
@@ -262,6 +264,45 @@ int wcpt_composite_bloom(wcpt_context* ctx, uint64_t dst, int format, const wcpt
                                               levels, lw, lh, ctx->d_bloom, ctx->d_bloom + texels,
                                               reinterpret_cast<void*>(dst), format == WCPT_COMPOSITE_RGBA8, ctx->stream),
             "bloom composite launch");
+    return WCPT_SUCCESS;
+}
+
+int wcpt_composite_denoise(wcpt_context* ctx, uint64_t guide, uint64_t guide_bytes, uint64_t dst, int format,
+                           const wcpt_denoise_params* p)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    rc = check_composite_target(ctx, dst, format);
+    if (rc) return rc;
+    if (!p) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "null denoise parameters");
+    if (!wcpt_denoise_params_ok(p->iterations, p->sigma_color, p->sigma_normal, p->sigma_depth))
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT,
+                         "denoise of %u iterations (1..6), sigma colour %g (> 0), normal %g, depth %g (finite, > 0)",
+                         p->iterations, (double)p->sigma_color, (double)p->sigma_normal, (double)p->sigma_depth);
+    if (ctx->layout.sharded)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "denoise needs the whole frame: the context holds %u of %u rows",
+                         ctx->layout.rows, ctx->layout.height);
+    const uint64_t need = (uint64_t)ctx->layout.width * ctx->layout.height * WCPT_DENOISE_RECORD_BYTES;
+    if (!guide || (guide & 15u) || guide_bytes < need)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "denoise guide: %llu bytes at a null or misaligned address, %llu needed",
+                         (unsigned long long)guide_bytes, (unsigned long long)need);
+    uint64_t off = 0;
+    Buffer* b = buffer_at(ctx, guide, off);
+    if (b && off + need > b->bytes)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "denoise guide holds %llu bytes, %llu needed",
+                         (unsigned long long)(b->bytes - off), (unsigned long long)need);
+    /* two images and the packed guide in one allocation; every part is written before it is read in each call, so a new
+     * screen size only moves the parts */
+    const uint64_t bytes = wcpt::denoise_scratch_bytes(ctx->layout.width, ctx->layout.height);
+    if (bytes > ctx->denoise_bytes) {
+        rc = grow(ctx, ctx->d_denoise, ctx->denoise_bytes, bytes, bytes, "hipMalloc(denoise scratch)");
+        if (rc) return rc;
+    }
+    HIP_TRY(ctx, wcpt::launch_composite_denoise(ctx->image, reinterpret_cast<const void*>(guide), ctx->layout.width,
+                                                ctx->layout.height, p->iterations, p->sigma_color, p->sigma_normal,
+                                                p->sigma_depth, ctx->d_denoise, reinterpret_cast<void*>(dst),
+                                                format == WCPT_COMPOSITE_RGBA8, ctx->stream),
+            "denoise composite launch");
     return WCPT_SUCCESS;
 }
 

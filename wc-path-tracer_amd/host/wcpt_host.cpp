@@ -6,6 +6,7 @@
  *   wcpt_camera_update  <- src/PathTracingRenderer.jai:22-36   (Camera Update)
  *   wcpt_scene_generate "default" <- src/PathTracingRenderer.jai:322-339 (Init's materials and spheres)
  *   wcpt_bloom_host     <- src/shaders/bloom.comp, composite.comp:44-45 through csrc/wcpt_bloom.h (the device's arithmetic)
+ *   wcpt_denoise_host   <- csrc/wcpt_denoise.h (the device's arithmetic; the reference has no denoiser)
  *
  * No GPU is needed for anything in this file.
  */
@@ -20,6 +21,7 @@
 
 #include "../../include/wcpt.h"
 #include "../csrc/wcpt_bloom.h"
+#include "../csrc/wcpt_denoise.h"
 #include "../csrc/bvh_refit.h"
 
 /* The runtime's last-error text (wcpt_runtime.hip), for the host utilities that name what they refuse. Weak: this file
@@ -893,6 +895,58 @@ void bloom_host(const float* rgba, uint32_t width, uint32_t height, const wcpt_b
         }
 }
 
+/* ------------------------------------------------------------------------------------------------ */
+/* Denoise: the iterations of csrc/wcpt_denoise.h over float4 arrays and the packed guide            */
+
+struct HostImage {
+    const float* texels; /* float4 per pixel */
+    int w;
+    void operator()(int x, int y, float rgba[4]) const { memcpy(rgba, texels + 4 * ((size_t)y * (size_t)w + (size_t)x), 16); }
+};
+
+struct HostGuide {
+    const uint32_t* row0; /* the plane of first rows, four words per pixel */
+    const uint32_t* row1;
+    int w;
+    void first(int x, int y, uint32_t r[4]) const { memcpy(r, row0 + 4 * ((size_t)y * (size_t)w + (size_t)x), 16); }
+    void second(int x, int y, uint32_t r[4]) const { memcpy(r, row1 + 4 * ((size_t)y * (size_t)w + (size_t)x), 16); }
+};
+
+void denoise_host(const float* rgba, const wcpt_primary_hit* records, uint32_t width, uint32_t height, uint32_t iterations,
+                  const wcpt_denoise_consts& k, float* out32, uint8_t* out8)
+{
+    const size_t pixels = (size_t)width * height;
+    std::vector<uint32_t> row0(pixels * 4), row1(pixels * 4);
+    for (size_t i = 0; i < pixels; i++) {
+        uint32_t rec[WCPT_DENOISE_RECORD_WORDS];
+        memcpy(rec, records + i, sizeof(rec));
+        wcpt_denoise_pack(rec, k.sigma_depth, &row0[4 * i], &row1[4 * i]);
+    }
+    const HostGuide guide{row0.data(), row1.data(), (int)width};
+    std::vector<float> image[2];
+    const float* src = rgba;
+    for (uint32_t it = 0; it < iterations; it++) {
+        std::vector<float>& dst = image[it & 1u];
+        dst.resize(pixels * 4);
+        const HostImage img{src, (int)width};
+        for (int y = 0; y < (int)height; y++)
+            for (int x = 0; x < (int)width; x++)
+                wcpt_denoise_texel(img, guide, (int)width, (int)height, x, y, 1 << it, k, &dst[4 * ((size_t)y * width + x)]);
+        src = dst.data();
+    }
+    for (size_t i = 0; i < pixels; i++) {
+        float o[4];
+        wcpt_composite_texel(src + 4 * i, o);
+        if (out32) memcpy(out32 + 4 * i, o, sizeof(o));
+        if (out8) {
+            out8[4 * i + 0] = wcpt_unorm8(o[0]);
+            out8[4 * i + 1] = wcpt_unorm8(o[1]);
+            out8[4 * i + 2] = wcpt_unorm8(o[2]);
+            out8[4 * i + 3] = 255;
+        }
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -1093,6 +1147,22 @@ int wcpt_bloom_host(const float* rgba, uint32_t width, uint32_t height, const wc
     if (n == 0) return WCPT_ERROR_INVALID_ARGUMENT;
     try {
         bloom_host(rgba, width, height, wcpt_bloom_make_curve(p->threshold, p->knee), n, lw, lh, out_rgba32f, out_rgba8);
+    } catch (...) {
+        return WCPT_ERROR_OUT_OF_HOST_MEMORY;
+    }
+    return WCPT_SUCCESS;
+}
+
+int wcpt_denoise_host(const float* rgba, const wcpt_primary_hit* guide, uint32_t width, uint32_t height,
+                      const wcpt_denoise_params* p, float* out_rgba32f, uint8_t* out_rgba8)
+{
+    static_assert(sizeof(wcpt_primary_hit) == WCPT_DENOISE_RECORD_BYTES, "wcpt_primary_hit");
+    if (!rgba || !guide || !p || !wcpt_denoise_params_ok(p->iterations, p->sigma_color, p->sigma_normal, p->sigma_depth))
+        return WCPT_ERROR_INVALID_ARGUMENT;
+    if (width == 0 || height == 0 || width > 0x7FFFFFFFu || height > 0x7FFFFFFFu) return WCPT_ERROR_INVALID_ARGUMENT;
+    try {
+        denoise_host(rgba, guide, width, height, p->iterations,
+                     wcpt_denoise_make_consts(p->sigma_color, p->sigma_normal, p->sigma_depth), out_rgba32f, out_rgba8);
     } catch (...) {
         return WCPT_ERROR_OUT_OF_HOST_MEMORY;
     }

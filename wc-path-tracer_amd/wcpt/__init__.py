@@ -3,7 +3,7 @@
 The compute lives in libwcpt.so (hand-written HIP for gfx950 behind the C-ABI of include/wcpt.h); this
 package is the Python host mirror used by tests and the benchmark.
 """
-from ._lib import (BloomParams, COUNTER_FIELDS, DRAW_COMMAND_DTYPE, EXPORTED_SYMBOLS, KERNEL_AUTO, KERNEL_MEGAKERNEL,
+from ._lib import (BloomParams, DenoiseParams, COUNTER_FIELDS, DRAW_COMMAND_DTYPE, EXPORTED_SYMBOLS, KERNEL_AUTO, KERNEL_MEGAKERNEL,
                    KERNEL_WAVEFRONT, LIB_PATH, MATERIAL_DIELECTRIC, MATERIAL_DTYPE, MATERIAL_METAL, NODE_DTYPE,
                    SCENE_DATA_DTYPE, SPHERE_DTYPE, PRIMARY_HIT_DTYPE, HIT_MISS, HIT_SPHERE, HIT_TRIANGLE, HIT_KIND_MASK,
                    HIT_FRONT, Camera, WcptError, lib)
@@ -16,7 +16,7 @@ __all__ = [
     "KERNEL_WAVEFRONT", "LIB_PATH", "MATERIAL_DIELECTRIC", "MATERIAL_DTYPE", "MATERIAL_METAL", "NODE_DTYPE",
     "SCENE_DATA_DTYPE", "SPHERE_DTYPE", "Camera", "WcptError", "lib", "Context", "DeviceScene",
     "PathTracingRenderer", "Editor", "Group", "group_unique_id", "scene", "device_count", "device_pci_bus_id", "runtime_version", "build_id",
-    "BloomParams", "bloom_levels", "bloom_host",
+    "BloomParams", "bloom_levels", "bloom_host", "DenoiseParams", "denoise_host",
     "PRIMARY_HIT_DTYPE", "HIT_MISS", "HIT_SPHERE", "HIT_TRIANGLE", "HIT_KIND_MASK", "HIT_FRONT",
 ]
 
@@ -72,4 +72,24 @@ def bloom_host(img, params=None):
     out8 = np.empty(a.shape, np.uint8)
     import ctypes as C
     _lib.check(lib.wcpt_bloom_host(_lib.ptr(a), a.shape[1], a.shape[0], C.byref(params), _lib.ptr(out32), _lib.ptr(out8)))
+    return out32, out8
+
+
+def denoise_host(img, guide, params=None):
+    """wcpt_denoise_host: what Context.composite(dst, denoise=params, guide=...) stores for the float4 image `img`
+    [H][W][4] and the primary-hit records `guide` [H][W] (PRIMARY_HIT_DTYPE), computed on the CPU by the same arithmetic
+    (no GPU needed): returns (rgba32f, rgba8)."""
+    import ctypes as C
+    import numpy as np
+    a = np.ascontiguousarray(img, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("denoise_host: an image of shape (height, width, 4)")
+    g = np.ascontiguousarray(guide, dtype=PRIMARY_HIT_DTYPE)
+    if g.shape != a.shape[:2]:
+        raise ValueError("denoise_host: one record per pixel, shape (height, width)")
+    params = DenoiseParams() if params is None else params
+    out32 = np.empty(a.shape, np.float32)
+    out8 = np.empty(a.shape, np.uint8)
+    _lib.check(lib.wcpt_denoise_host(_lib.ptr(a), _lib.ptr(g), a.shape[1], a.shape[0], C.byref(params), _lib.ptr(out32),
+                                     _lib.ptr(out8)))
     return out32, out8

@@ -186,6 +186,17 @@ class BloomParams(C.Structure):
 BLOOM_MAX_LEVELS = 16  # the arrays of wcpt_bloom_levels
 
 
+class DenoiseParams(C.Structure):
+    """wcpt_denoise_params (include/wcpt.h): the callers' defaults are 5 iterations, sigma_color 4.0, sigma_normal 0.5,
+    sigma_depth 0.05."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float)]
+
+    def __init__(self, iterations: int = 5, sigma_color: float = 4.0, sigma_normal: float = 0.5,
+                 sigma_depth: float = 0.05):
+        super().__init__(iterations, sigma_color, sigma_normal, sigma_depth)
+
+
 class SceneC(C.Structure):
     _fields_ = [("mesh", Mesh), ("materials", C.c_void_p), ("material_count", C.c_uint32),
                 ("spheres", C.c_void_p), ("sphere_count", C.c_uint32), ("camera", Camera)]
@@ -228,6 +239,8 @@ _PROTOTYPES = {
     "wcpt_composite_bloom": (_i, [_p, _u64, _i, C.POINTER(BloomParams)]),
     "wcpt_bloom_levels": (_i, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "wcpt_bloom_host": (_i, [_p, _u32, _u32, C.POINTER(BloomParams), _p, _p]),
+    "wcpt_composite_denoise": (_i, [_p, _u64, _u64, _u64, _i, C.POINTER(DenoiseParams)]),
+    "wcpt_denoise_host": (_i, [_p, _p, _u32, _u32, C.POINTER(DenoiseParams), _p, _p]),
     "wcpt_render": (_i, [_p, _p, _u64, _u64, _u64]),
     "wcpt_sync": (_i, [_p]),
     "wcpt_primary_cache_stats": (_i, [_p, C.POINTER(_u64), C.POINTER(_u64)]),

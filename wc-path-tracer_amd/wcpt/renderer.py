@@ -170,10 +170,22 @@ class Context:
         self._chk(lib.wcpt_image_upload(self.h, ptr(a), a.nbytes))
 
     # -- dispatch ---------------------------------------------------------------------------------------
-    def composite(self, dst: int, rgba8: bool = False, bloom=None):
+    def composite(self, dst: int, rgba8: bool = False, bloom=None, denoise=None, guide: int | None = None,
+                  guide_bytes: int | None = None):
         """composite.comp into device memory at `dst` (asynchronous); with `bloom` (a BloomParams) its Bloom branch is
-        taken: bloom.comp's pyramid of the image is added before gamma and the tonemap (wcpt_composite_bloom)."""
-        if bloom is None:
+        taken: bloom.comp's pyramid of the image is added before gamma and the tonemap (wcpt_composite_bloom). With
+        `denoise` (a DenoiseParams) the image goes through the guided a-trous filter first (wcpt_composite_denoise):
+        `guide` is the device address of the frame's primary-hit records (trace_primary) and `guide_bytes` the size of
+        the memory there (default width * height * 48). Denoise and bloom in one call are not provided."""
+        if denoise is not None:
+            if bloom is not None:
+                raise ValueError("composite: denoise and bloom in one call are not provided")
+            if guide is None:
+                raise ValueError("composite: denoise needs the guide (the records of trace_primary)")
+            if guide_bytes is None:
+                guide_bytes = self.width * self.height * PRIMARY_HIT_DTYPE.itemsize
+            self._chk(lib.wcpt_composite_denoise(self.h, guide, guide_bytes, dst, 1 if rgba8 else 0, C.byref(denoise)))
+        elif bloom is None:
             self._chk(lib.wcpt_composite(self.h, dst, 1 if rgba8 else 0))
         else:
             self._chk(lib.wcpt_composite_bloom(self.h, dst, 1 if rgba8 else 0, C.byref(bloom)))
@@ -443,6 +455,9 @@ class PathTracingRenderer:
         self._mat_buf = self._sph_buf = self._draw_buf = None
         self._mesh_bufs = []
         self._mesh_info = []             # per mesh: (vb, ib, nb, vertex count, index count, nodes used), for UpdateMesh
+        self._guide_buf = None           # Composite(denoise=...): the primary-hit records of the accumulated frames
+        self._guide_bytes = 0
+        self._guide_stale = True
 
     # Init :272-343 — LoadModel + materials/spheres + UpdateMaterials
     def Init(self, model_path: str | None = None, scene: "_scene.HostScene | None" = None, build: str = "host",
@@ -511,6 +526,7 @@ class PathTracingRenderer:
             self.ctx.buffer_upload(vb, pos)
             self.ctx.buffer_upload(nb, new.nodes)
         self.renderedFramesCount = 0
+        self._guide_stale = True
 
     # PushMaterial :492-496
     def PushMaterial(self) -> int:
@@ -538,6 +554,7 @@ class PathTracingRenderer:
     def Resize(self, size):
         self.CreateScreen(size)
         self.renderedFramesCount = 0
+        self._guide_stale = True
 
     def scene_data(self, camera: Camera) -> np.ndarray:
         """SceneData as Render fills it (:410-422); the camera's matrices must be up to date (Update :22)."""
@@ -556,12 +573,37 @@ class PathTracingRenderer:
     # Render :399-457
     def Render(self, camera: Camera):
         sd = self.scene_data(camera)
+        if self.renderedFramesCount == 0:
+            self._guide_stale = True     # the accumulation restarts: something moved
         self.renderedFramesCount += 1    # :423 (the editor adds its own +1 when the camera is still)
         self.ctx.render(sd, self.ctx.buffer_address(self._mat_buf), self.ctx.buffer_address(self._sph_buf),
                         self.ctx.buffer_address(self._draw_buf))
 
     def Readback(self) -> np.ndarray:
         return self.ctx.readback()
+
+    def Composite(self, camera: Camera, dst: int, rgba8: bool = False, denoise=None):
+        """The display step into device memory at `dst` (Context.composite). With `denoise` (a DenoiseParams) the
+        renderer keeps a guide buffer of its own and traces it with Context.trace_primary only when it is stale: on first
+        use, after Resize, after UpdateMesh, and after any Render whose renderedFramesCount was 0 -- the editor's
+        protocol: whatever moves, the count restarts."""
+        if denoise is None:
+            self.ctx.composite(dst, rgba8=rgba8)
+            return
+        w, h = self.renderSize
+        nbytes = w * h * PRIMARY_HIT_DTYPE.itemsize
+        if self._guide_buf is None or self._guide_bytes < nbytes:
+            if self._guide_buf is not None:
+                self.ctx.buffer_free(self._guide_buf)
+            self._guide_buf = self.ctx.buffer_alloc(nbytes)
+            self._guide_bytes = nbytes
+            self._guide_stale = True
+        guide = self.ctx.buffer_address(self._guide_buf)
+        if self._guide_stale:
+            self.ctx.trace_primary(self.scene_data(camera), self.ctx.buffer_address(self._sph_buf),
+                                   self.ctx.buffer_address(self._draw_buf), guide, self._guide_bytes)
+            self._guide_stale = False
+        self.ctx.composite(dst, rgba8=rgba8, denoise=denoise, guide=guide, guide_bytes=self._guide_bytes)
 
     def Pick(self, camera: Camera, x: int, y: int):
         """What pixel (x, y) of the frame shows from `camera` (wcpt_pick): (record, position) -- the PRIMARY_HIT_DTYPE
@@ -579,10 +621,10 @@ class PathTracingRenderer:
         for b in self._mesh_bufs:
             self.ctx.buffer_free(b)
         self._mesh_bufs = []
-        for b in (self._mat_buf, self._sph_buf, self._draw_buf):
+        for b in (self._mat_buf, self._sph_buf, self._draw_buf, self._guide_buf):
             if b is not None:
                 self.ctx.buffer_free(b)
-        self._mat_buf = self._sph_buf = self._draw_buf = None
+        self._mat_buf = self._sph_buf = self._draw_buf = self._guide_buf = None
         self.ctx.close()
 
 
