@@ -9,6 +9,9 @@
  *   display (composite.comp)                     gamma + PBR Neutral -> RGBA8 -> PPM file
  *   denoised display                             the last frame's primary-hit records as the guide (wcpt_trace_primary),
  *                                                wcpt_composite_denoise -> RGBA8 -> <out>_denoised.ppm beside it
+ *   a short orbit                                six one-sample frames, the camera yawing 1.5 degrees a frame as in a
+ *                                                drag (every frame restarts the accumulation), each through
+ *                                                wcpt_composite_temporal -> the last one as <out>_temporal.ppm
  *
  *   usage: editor_loop [scene=cornell] [width=640] [height=360] [frames=8] [out.ppm] [--move-at K]
  *
@@ -181,6 +184,35 @@ int main(int argc, char** argv)
         CHECK(ctx, wcpt_composite_denoise(ctx, a_guide, guide_bytes, wcpt_buffer_device_address(ctx, b_out),
                                           WCPT_COMPOSITE_RGBA8, &dn));
         CHECK(ctx, wcpt_sync(ctx));
+        CHECK(ctx, write_ppm(ctx, b_out, W, H, path));
+    }
+
+    /* ---- a short orbit: every frame moves the camera, so every frame is a fresh one-sample image (editor.jai:149-152)
+     * and a restart of the temporal stage, which looks the previous result up where each pixel's surface point was ---- */
+    if (frames > 0) {
+        const uint64_t guide_bytes = (uint64_t)W * H * sizeof(wcpt_primary_hit);
+        const uint64_t a_guide = wcpt_buffer_device_address(ctx, b_guide);
+        const wcpt_temporal_params tp = {32, 0.9f, 0.05f, 0}; /* the callers' defaults */
+        char path[1024];
+        const char* dot = strrchr(out_path, '.');
+        const int stem = dot ? (int)(dot - out_path) : (int)strlen(out_path);
+        snprintf(path, sizeof(path), "%.*s_temporal%s", stem, out_path, dot ? dot : "");
+        wcpt_scene_data sd = last_sd;
+        CHECK(ctx, wcpt_temporal_reset(ctx));
+        for (int f = 0; f < 6; f++) {
+            cam.yaw += 1.5f;
+            CHECK(ctx, wcpt_camera_update(&cam, (float)W / (float)H));
+            memcpy(sd.inverseProjection, cam.inverseProjection, sizeof(sd.inverseProjection));
+            memcpy(sd.inverseView, cam.inverseView, sizeof(sd.inverseView));
+            memcpy(sd.position, cam.position, sizeof(sd.position));
+            sd.renderedFramesCount = 0;
+            CHECK(ctx, wcpt_render(ctx, &sd, a_mat, a_sph, a_draw));
+            CHECK(ctx, wcpt_trace_primary(ctx, &sd, a_sph, a_draw, a_guide, guide_bytes));
+            CHECK(ctx, wcpt_composite_temporal(ctx, &sd, sd.renderedFramesCount + 1u, 1, a_guide, guide_bytes,
+                                               wcpt_buffer_device_address(ctx, b_out), WCPT_COMPOSITE_RGBA8, &tp, NULL));
+        }
+        CHECK(ctx, wcpt_sync(ctx));
+        printf("orbit: 6 frames of 1 sample, 1.5 degrees apart, accumulated by wcpt_composite_temporal\n");
         CHECK(ctx, write_ppm(ctx, b_out, W, H, path));
     }
 

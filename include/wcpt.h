@@ -630,6 +630,67 @@ int      wcpt_composite_denoise(wcpt_context* ctx, uint64_t guide, uint64_t guid
 int      wcpt_denoise_host(const float* rgba, const wcpt_primary_hit* guide, uint32_t width, uint32_t height,
                            const wcpt_denoise_params* p, float* out_rgba32f, uint8_t* out_rgba8);
 
+/* ---- temporal reprojection for the display step. Added under ABI 4. ---------------------------------------------- */
+/* While anything moves, every displayed frame is a fresh one-sample image and every earlier frame is thrown away, although
+ * the surfaces on screen are mostly those of a frame ago. wcpt_composite_temporal is wcpt_composite (or, with `d`,
+ * wcpt_composite_denoise) of a blend of the accumulation image with the previous result, looked up where each pixel's
+ * surface point was a frame ago: the temporal half of an SVGF-style pipeline. A sequence is the calls between two restarts
+ * of the accumulation. A restart call reprojects each pixel's hit point (the sky: its direction) into the previous
+ * sequence's frame, gathers the four surrounding texels of the previous output that show the same surface (the same
+ * identity, a normal within normal_min, a distance from the pixel's tangent plane within depth_tol of its hit distance),
+ * and keeps their weighted mean as the sequence's `base` with the samples it counts, at most max_history. Every call blends
+ * base with the accumulation image by the two sample counts, so a still camera converges as it does without this stage.
+ * csrc/wcpt_temporal.h fixes the rule and the order of every operation; DESIGN.md section 8 has what it is worth and the
+ * limit the reference's seed sets. Callers' defaults: 32, 0.9, 0.05. */
+typedef struct wcpt_temporal_params {
+    uint32_t max_history;  /* 1..65536: the samples a history may count */
+    float    normal_min;   /* finite, in [-1, 1]: the least dot product of the two normals */
+    float    depth_tol;    /* finite, > 0: relative to the pixel's hit distance */
+    uint32_t _pad;         /* ignored */
+} wcpt_temporal_params;
+/* `scene` is the scene data of the accumulated frames (of it inverseProjection, inverseView and position are read, the
+ * fields wcpt_trace_primary reads: the reprojection inverts what the rays did, whatever matrix convention the host has),
+ * `frames` the number of samples in the accumulation image (the last render's renderedFramesCount + 1), `guide` and
+ * `guide_bytes` the records of wcpt_trace_primary for that camera as for wcpt_composite_denoise. restart != 0 says that the
+ * accumulation restarted since the previous call and `guide` is the new sequence's guide; with restart == 0, `guide` must be
+ * the sequence's guide again and only the denoise reads it. The first call, and the first after wcpt_temporal_reset,
+ * wcpt_create_screen, wcpt_resize or a change of the context's rows, is a restart without history whatever `restart` says.
+ * `d` NULL: the blend goes through the display step as wcpt_composite does it; otherwise through wcpt_composite_denoise's
+ * filter first. Asynchronous on the context's stream, same `dst` and `format` as wcpt_composite; like wcpt_composite it first
+ * orders the stream behind both frame-overlap pipes. It reads the accumulation image and never writes it, leaves the primary
+ * cache, the frame preparation, wcpt_last_kernel, wcpt_last_arith and every counter alone, and always runs exact. Its
+ * scratch (120 bytes per pixel: the previous output with its lengths and packed guide twice, and base; with `d` also
+ * wcpt_composite_denoise's 64) is the context's: allocated by the first call, laid out again on a new screen size, freed by
+ * wcpt_destroy. A guide or a camera that does not belong to the image gives a wrong picture but never an access outside the
+ * buffers: guide words are only compared and multiplied, and a tap's position comes from a range-checked coordinate.
+ * WCPT_ERROR_NO_SCREEN without a screen. WCPT_ERROR_INVALID_ARGUMENT, with nothing launched and no state changed: a null
+ * `scene` or `t`, max_history outside 1..65536, a normal_min that is NaN or outside [-1, 1], a depth_tol that is NaN, <= 0 or
+ * infinite, frames == 0, a camera whose inverseProjection or the upper-left 3x3 of whose inverseView is singular or whose
+ * corner pixels do not come back to their centres within 1e-3 pixel (a projection that is not a plain perspective), what
+ * wcpt_composite_denoise refuses about `guide`, `dst`, `format` and `d`, and a context that does not hold the whole frame.
+ * Not provided: halos for row blocks, a temporal group payload, bloom in the same call. */
+int      wcpt_composite_temporal(wcpt_context* ctx, const wcpt_scene_data* scene, uint32_t frames, int restart,
+                                 uint64_t guide, uint64_t guide_bytes, uint64_t dst, int format,
+                                 const wcpt_temporal_params* t, const wcpt_denoise_params* d);
+/* Drops the history: the next wcpt_composite_temporal is a restart without history. For what the records cannot see: a
+ * material, light or mesh change. Host only. */
+int      wcpt_temporal_reset(wcpt_context* ctx);
+/* One call of wcpt_composite_temporal's state sequence on the CPU by the same arithmetic (csrc/wcpt_temporal.h), stateless:
+ * the caller carries the state. `rgba` is the accumulation image (float4), `guide` and `scene` its records and scene data.
+ * restart != 0: `base` (3 floats per pixel) and `n_b` (1 float per pixel) are written, from the history -- the previous
+ * call's out_rgba and out_length with the records and scene data of the sequence they belong to; a NULL hist_rgba means no
+ * history and the other three are then not read -- and then blended. restart == 0: base and n_b are read (the sequence's)
+ * and left as they are, and the history arguments are not read. Either way out_rgba (float4) and out_length (1 float per
+ * pixel) receive the new output and its lengths; they must not alias the history. Display and denoise of out_rgba go through
+ * wcpt_denoise_host or the composite of the oracle. Refuses as wcpt_composite_temporal does about `scene`, `hist_scene`,
+ * `frames` and `t` (and a null image, guide or output, a history without all four parts, a frame without pixels), writing
+ * nothing. No GPU needed. */
+int      wcpt_temporal_host(const float* rgba, uint32_t frames, int restart, const wcpt_primary_hit* guide,
+                            const wcpt_scene_data* scene, uint32_t width, uint32_t height, const wcpt_temporal_params* t,
+                            const float* hist_rgba, const float* hist_length, const wcpt_primary_hit* hist_guide,
+                            const wcpt_scene_data* hist_scene, float* base, float* n_b, float* out_rgba,
+                            float* out_length);
+
 /* Wavefront trace-loop phase timers of the last wcpt_render_counters call with WCPT_OPTION_DIAGNOSTICS set
  * (s_memtime cycles summed over waves): {fetch, leaf, interior, pop, epilogue, waves, iterations, -}. */
 int      wcpt_read_diagnostics(wcpt_context* ctx, uint64_t* out, uint32_t n);

@@ -14,6 +14,9 @@
 #include "row_map.h"
 #include "wf_plan.h"
 
+struct wcpt_temporal_camera; /* wcpt_temporal.h */
+struct wcpt_temporal_consts;
+
 namespace wcpt {
 
 /* Traversal stack entries per lane. The reference declares 32 (pathTracer.comp:151), which a depth-32
@@ -229,6 +232,20 @@ uint64_t denoise_scratch_bytes(uint32_t width, uint32_t height);
 hipError_t launch_composite_denoise(const float4* img, const void* records, uint32_t width, uint32_t height,
                                     uint32_t iterations, float sigma_color, float sigma_normal, float sigma_depth,
                                     void* scratch, void* dst, bool rgba8, hipStream_t stream);
+/* Temporal reprojection in front of the display step (pt_temporal.hip; the rule of wcpt_temporal.h) over `scratch` of
+ * temporal_scratch_bytes bytes, which holds the sequence's state in two sides. launch_temporal_reproject is a restart call:
+ * from the records and the accumulation image `img` (camera position `position`) and, with has_hist, side `old_side` seen
+ * by `hist_cam`, it writes base, n_b and the other side. launch_temporal_blend is any other call, in place in `side`.
+ * `store`: 0 nothing more (temporal_hist_image of the written side is then the denoise launch's source), 1 the display step
+ * into rgba32f at `dst`, 2 into RGBA8. One launch each; `img` is only read. */
+uint64_t temporal_scratch_bytes(uint32_t width, uint32_t height);
+const float4* temporal_hist_image(void* scratch, uint32_t width, uint32_t height, uint32_t side);
+hipError_t launch_temporal_reproject(const float4* img, const void* records, uint32_t width, uint32_t height,
+                                     const float position[3], bool has_hist, const wcpt_temporal_camera& hist_cam,
+                                     uint32_t old_side, float frames, const wcpt_temporal_consts& k, void* scratch, void* dst,
+                                     int store, hipStream_t stream);
+hipError_t launch_temporal_blend(const float4* img, uint32_t width, uint32_t height, uint32_t side, float frames,
+                                 const wcpt_temporal_consts& k, void* scratch, void* dst, int store, hipStream_t stream);
 /* wcpt_bvh_build_device (pt_bvh_build.hip; the rule in bvh_midpoint.h): the midpoint BVH of the triangles
  * indices[0 .. index_count) over `vertices` into `nodes` (2 * index_count / 3 of them) with `indices` permuted, in
  * `scratch` of bvh_build_scratch_bytes(index_count) bytes. Blocks the host: *status is 0 and *nodes_used the node count

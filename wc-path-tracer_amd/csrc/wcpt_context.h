@@ -100,6 +100,15 @@ struct wcpt_context {
     uint64_t bloom_bytes = 0;
     void* d_denoise = nullptr;         /* wcpt_composite_denoise: two float4 images, then the packed guide (on first use) */
     uint64_t denoise_bytes = 0;
+    void* d_temporal = nullptr;        /* wcpt_composite_temporal: the sequence's state in two sides (pt_temporal.hip; on first use) */
+    uint64_t temporal_bytes = 0;
+    /* the history wcpt_composite_temporal carries: dropped by wcpt_temporal_reset and by every new layout of the screen */
+    struct TemporalState {
+        bool valid = false;
+        uint32_t side = 0;             /* the side of d_temporal that holds the last output */
+        float F[9] = {};               /* the camera that side's guide belongs to (wcpt_temporal.h wcpt_temporal_camera) */
+        float position[3] = {};
+    } temporal;
     void* d_bvh = nullptr;             /* wcpt_bvh_build_device / _sah_device / wcpt_bvh_refit_device: their scratch (on first use, grown on demand) */
     uint64_t bvh_bytes = 0;
     void* d_bvh_bins = nullptr;        /* wcpt_bvh_build_sah_device: the bins of a level's open nodes (grown on demand) */

@@ -196,6 +196,7 @@ int wcpt_destroy(wcpt_context* ctx)
     if (ctx->d_scan) (void)hipFree(ctx->d_scan);
     if (ctx->d_bloom) (void)hipFree(ctx->d_bloom);
     if (ctx->d_denoise) (void)hipFree(ctx->d_denoise);
+    if (ctx->d_temporal) (void)hipFree(ctx->d_temporal);
     if (ctx->d_bvh) (void)hipFree(ctx->d_bvh);
     if (ctx->d_bvh_bins) (void)hipFree(ctx->d_bvh_bins);
     for (auto& p : ctx->events) {

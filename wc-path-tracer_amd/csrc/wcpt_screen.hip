@@ -2,11 +2,12 @@
  * wcpt_screen.hip — C-ABI runtime, the output image (CreateScreen / Resize): the frame's size and the rows of it the
  * context holds (screen_layout.h states every rule; here are their messages and the device's part), an external image,
  * the gather output, readback and upload, and the display step (wcpt_composite, wcpt_composite_bloom,
- * wcpt_composite_denoise).
+ * wcpt_composite_denoise, wcpt_composite_temporal).
  */
 #include "wcpt_context.h"
 #include "wcpt_bloom.h"
 #include "wcpt_denoise.h"
+#include "wcpt_temporal.h"
 
 using namespace wcpt::rt;
 
@@ -38,6 +39,7 @@ uint64_t layout_bytes(const wcpt::ScreenLayout& l) { return (uint64_t)l.width * 
 int apply_layout(wcpt_context* ctx, const wcpt::ScreenLayout& next, bool zero)
 {
     wcpt::ScreenLayout& l = ctx->layout;
+    ctx->temporal.valid = false; /* wcpt_composite_temporal's history belongs to the layout it was made in */
     l.sharded = next.sharded;
     l.stripe = next.stripe;
     l.period = next.period;
@@ -267,6 +269,48 @@ int wcpt_composite_bloom(wcpt_context* ctx, uint64_t dst, int format, const wcpt
     return WCPT_SUCCESS;
 }
 
+namespace {
+
+/* What wcpt_composite_denoise and wcpt_composite_temporal check about the denoise parameters and the guide: the context
+ * holds the whole frame, and the guide's memory holds a record per pixel. */
+int check_denoise_params(wcpt_context* ctx, const wcpt_denoise_params* p)
+{
+    if (!p) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "null denoise parameters");
+    if (!wcpt_denoise_params_ok(p->iterations, p->sigma_color, p->sigma_normal, p->sigma_depth))
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT,
+                         "denoise of %u iterations (1..6), sigma colour %g (> 0), normal %g, depth %g (finite, > 0)",
+                         p->iterations, (double)p->sigma_color, (double)p->sigma_normal, (double)p->sigma_depth);
+    return WCPT_SUCCESS;
+}
+
+int check_guide(wcpt_context* ctx, uint64_t guide, uint64_t guide_bytes, const char* who)
+{
+    if (ctx->layout.sharded)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "%s needs the whole frame: the context holds %u of %u rows", who,
+                         ctx->layout.rows, ctx->layout.height);
+    const uint64_t need = (uint64_t)ctx->layout.width * ctx->layout.height * WCPT_DENOISE_RECORD_BYTES;
+    if (!guide || (guide & 15u) || guide_bytes < need)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "%s guide: %llu bytes at a null or misaligned address, %llu needed",
+                         who, (unsigned long long)guide_bytes, (unsigned long long)need);
+    uint64_t off = 0;
+    Buffer* b = buffer_at(ctx, guide, off);
+    if (b && off + need > b->bytes)
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "%s guide holds %llu bytes, %llu needed", who,
+                         (unsigned long long)(b->bytes - off), (unsigned long long)need);
+    return WCPT_SUCCESS;
+}
+
+/* two images and the packed guide in one allocation; every part is written before it is read in each call, so a new
+ * screen size only moves the parts */
+int grow_denoise_scratch(wcpt_context* ctx)
+{
+    const uint64_t bytes = wcpt::denoise_scratch_bytes(ctx->layout.width, ctx->layout.height);
+    if (bytes > ctx->denoise_bytes) return grow(ctx, ctx->d_denoise, ctx->denoise_bytes, bytes, bytes, "hipMalloc(denoise scratch)");
+    return WCPT_SUCCESS;
+}
+
+} // namespace
+
 int wcpt_composite_denoise(wcpt_context* ctx, uint64_t guide, uint64_t guide_bytes, uint64_t dst, int format,
                            const wcpt_denoise_params* p)
 {
@@ -274,35 +318,91 @@ int wcpt_composite_denoise(wcpt_context* ctx, uint64_t guide, uint64_t guide_byt
     if (rc) return rc;
     rc = check_composite_target(ctx, dst, format);
     if (rc) return rc;
-    if (!p) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "null denoise parameters");
-    if (!wcpt_denoise_params_ok(p->iterations, p->sigma_color, p->sigma_normal, p->sigma_depth))
-        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT,
-                         "denoise of %u iterations (1..6), sigma colour %g (> 0), normal %g, depth %g (finite, > 0)",
-                         p->iterations, (double)p->sigma_color, (double)p->sigma_normal, (double)p->sigma_depth);
-    if (ctx->layout.sharded)
-        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "denoise needs the whole frame: the context holds %u of %u rows",
-                         ctx->layout.rows, ctx->layout.height);
-    const uint64_t need = (uint64_t)ctx->layout.width * ctx->layout.height * WCPT_DENOISE_RECORD_BYTES;
-    if (!guide || (guide & 15u) || guide_bytes < need)
-        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "denoise guide: %llu bytes at a null or misaligned address, %llu needed",
-                         (unsigned long long)guide_bytes, (unsigned long long)need);
-    uint64_t off = 0;
-    Buffer* b = buffer_at(ctx, guide, off);
-    if (b && off + need > b->bytes)
-        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "denoise guide holds %llu bytes, %llu needed",
-                         (unsigned long long)(b->bytes - off), (unsigned long long)need);
-    /* two images and the packed guide in one allocation; every part is written before it is read in each call, so a new
-     * screen size only moves the parts */
-    const uint64_t bytes = wcpt::denoise_scratch_bytes(ctx->layout.width, ctx->layout.height);
-    if (bytes > ctx->denoise_bytes) {
-        rc = grow(ctx, ctx->d_denoise, ctx->denoise_bytes, bytes, bytes, "hipMalloc(denoise scratch)");
-        if (rc) return rc;
-    }
+    rc = check_denoise_params(ctx, p);
+    if (rc) return rc;
+    rc = check_guide(ctx, guide, guide_bytes, "denoise");
+    if (rc) return rc;
+    rc = grow_denoise_scratch(ctx);
+    if (rc) return rc;
     HIP_TRY(ctx, wcpt::launch_composite_denoise(ctx->image, reinterpret_cast<const void*>(guide), ctx->layout.width,
                                                 ctx->layout.height, p->iterations, p->sigma_color, p->sigma_normal,
                                                 p->sigma_depth, ctx->d_denoise, reinterpret_cast<void*>(dst),
                                                 format == WCPT_COMPOSITE_RGBA8, ctx->stream),
             "denoise composite launch");
+    return WCPT_SUCCESS;
+}
+
+int wcpt_composite_temporal(wcpt_context* ctx, const wcpt_scene_data* scene, uint32_t frames, int restart, uint64_t guide,
+                            uint64_t guide_bytes, uint64_t dst, int format, const wcpt_temporal_params* t,
+                            const wcpt_denoise_params* d)
+{
+    static_assert(WCPT_TEMPORAL_RECORD_BYTES == WCPT_DENOISE_RECORD_BYTES, "one guide for both stages");
+    int rc = bind(ctx);
+    if (rc) return rc;
+    rc = check_composite_target(ctx, dst, format);
+    if (rc) return rc;
+    if (!scene || !t) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "null temporal scene or parameters");
+    if (!wcpt_temporal_params_ok(t->max_history, t->normal_min, t->depth_tol))
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT,
+                         "temporal history of %u samples (1..65536), normal_min %g (-1..1), depth_tol %g (finite, > 0)",
+                         t->max_history, (double)t->normal_min, (double)t->depth_tol);
+    if (frames == 0) return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT, "temporal: an accumulation image of 0 frames");
+    if (d) {
+        rc = check_denoise_params(ctx, d);
+        if (rc) return rc;
+    }
+    rc = check_guide(ctx, guide, guide_bytes, "temporal");
+    if (rc) return rc;
+    const uint32_t width = ctx->layout.width, height = ctx->layout.height;
+    wcpt_temporal_camera cam;
+    if (!wcpt_temporal_make_camera(scene->inverseProjection, scene->inverseView, scene->position, width, height, &cam))
+        return set_error(ctx, WCPT_ERROR_INVALID_ARGUMENT,
+                         "temporal: a singular camera matrix, or not a plain perspective (a corner pixel misses its centre)");
+    /* every part of a side is written before it is read, and the history does not outlive a layout (apply_layout) */
+    const uint64_t bytes = wcpt::temporal_scratch_bytes(width, height);
+    if (bytes > ctx->temporal_bytes) {
+        ctx->temporal.valid = false;
+        rc = grow(ctx, ctx->d_temporal, ctx->temporal_bytes, bytes, bytes, "hipMalloc(temporal scratch)");
+        if (rc) return rc;
+    }
+    if (d) {
+        rc = grow_denoise_scratch(ctx);
+        if (rc) return rc;
+    }
+    wcpt_context::TemporalState& st = ctx->temporal;
+    const wcpt_temporal_consts k = wcpt_temporal_make_consts(t->max_history, t->normal_min, t->depth_tol);
+    const int store = d ? 0 : (format == WCPT_COMPOSITE_RGBA8 ? 2 : 1);
+    void* const out = reinterpret_cast<void*>(dst);
+    if (restart || !st.valid) {
+        wcpt_temporal_camera hist_cam;
+        memcpy(hist_cam.F, st.F, sizeof(st.F));
+        memcpy(hist_cam.position, st.position, sizeof(st.position));
+        HIP_TRY(ctx, wcpt::launch_temporal_reproject(ctx->image, reinterpret_cast<const void*>(guide), width, height,
+                                                     cam.position, st.valid, hist_cam, st.side, (float)frames, k,
+                                                     ctx->d_temporal, out, store, ctx->stream),
+                "temporal reproject launch");
+        st.side = st.valid ? (st.side ^ 1u) : ((st.side & 1u) ^ 1u);
+        st.valid = true;
+        memcpy(st.F, cam.F, sizeof(st.F));
+        memcpy(st.position, cam.position, sizeof(st.position));
+    } else {
+        HIP_TRY(ctx, wcpt::launch_temporal_blend(ctx->image, width, height, st.side, (float)frames, k, ctx->d_temporal, out,
+                                                 store, ctx->stream),
+                "temporal blend launch");
+    }
+    if (d)
+        HIP_TRY(ctx, wcpt::launch_composite_denoise(wcpt::temporal_hist_image(ctx->d_temporal, width, height, st.side),
+                                                    reinterpret_cast<const void*>(guide), width, height, d->iterations,
+                                                    d->sigma_color, d->sigma_normal, d->sigma_depth, ctx->d_denoise, out,
+                                                    format == WCPT_COMPOSITE_RGBA8, ctx->stream),
+                "temporal denoise launch");
+    return WCPT_SUCCESS;
+}
+
+int wcpt_temporal_reset(wcpt_context* ctx)
+{
+    if (!ctx) return set_error(nullptr, WCPT_ERROR_INVALID_HANDLE, "null context");
+    ctx->temporal.valid = false;
     return WCPT_SUCCESS;
 }
 

@@ -7,6 +7,7 @@
  *   wcpt_scene_generate "default" <- src/PathTracingRenderer.jai:322-339 (Init's materials and spheres)
  *   wcpt_bloom_host     <- src/shaders/bloom.comp, composite.comp:44-45 through csrc/wcpt_bloom.h (the device's arithmetic)
  *   wcpt_denoise_host   <- csrc/wcpt_denoise.h (the device's arithmetic; the reference has no denoiser)
+ *   wcpt_temporal_host  <- csrc/wcpt_temporal.h (the device's arithmetic; the reference has no temporal stage)
  *
  * No GPU is needed for anything in this file.
  */
@@ -22,6 +23,7 @@
 #include "../../include/wcpt.h"
 #include "../csrc/wcpt_bloom.h"
 #include "../csrc/wcpt_denoise.h"
+#include "../csrc/wcpt_temporal.h"
 #include "../csrc/bvh_refit.h"
 
 /* The runtime's last-error text (wcpt_runtime.hip), for the host utilities that name what they refuse. Weak: this file
@@ -896,6 +898,58 @@ void bloom_host(const float* rgba, uint32_t width, uint32_t height, const wcpt_b
 }
 
 /* ------------------------------------------------------------------------------------------------ */
+/* Temporal reprojection: one call of csrc/wcpt_temporal.h's state sequence over host arrays          */
+
+struct HostHistory {
+    const uint32_t* row0; /* the packed guide of the history's frame, four words per pixel and plane */
+    const uint32_t* row1;
+    const float* len;
+    const float* texels;  /* float4 per pixel */
+    int w;
+    size_t at(int x, int y) const { return (size_t)y * (size_t)w + (size_t)x; }
+    void first(int x, int y, uint32_t r[4]) const { memcpy(r, row0 + 4 * at(x, y), 16); }
+    void second(int x, int y, uint32_t r[4]) const { memcpy(r, row1 + 4 * at(x, y), 16); }
+    float length(int x, int y) const { return len[at(x, y)]; }
+    void colour(int x, int y, float rgba[4]) const { memcpy(rgba, texels + 4 * at(x, y), 16); }
+};
+
+void temporal_host(const float* rgba, float f, bool restart, const wcpt_primary_hit* records, const float position[3],
+                   uint32_t width, uint32_t height, const wcpt_temporal_consts& k, const float* hist_rgba,
+                   const float* hist_length, const wcpt_primary_hit* hist_records, const wcpt_temporal_camera* hist_cam,
+                   float* base, float* n_b, float* out_rgba, float* out_length)
+{
+    const size_t pixels = (size_t)width * height;
+    if (restart) {
+        std::vector<uint32_t> row0, row1;
+        if (hist_rgba) {
+            row0.resize(pixels * 4);
+            row1.resize(pixels * 4);
+            for (size_t i = 0; i < pixels; i++) {
+                uint32_t rec[WCPT_TEMPORAL_RECORD_WORDS];
+                memcpy(rec, hist_records + i, sizeof(rec));
+                wcpt_temporal_pack(rec, hist_cam->position, &row0[4 * i], &row1[4 * i]);
+            }
+        }
+        const HostHistory hist{row0.data(), row1.data(), hist_length, hist_rgba, (int)width};
+        for (int y = 0; y < (int)height; y++)
+            for (int x = 0; x < (int)width; x++) {
+                const size_t i = (size_t)y * width + x;
+                if (!hist_rgba) {
+                    base[3 * i] = base[3 * i + 1] = base[3 * i + 2] = 0.0f;
+                    n_b[i] = 0.0f;
+                    continue;
+                }
+                uint32_t rec[WCPT_TEMPORAL_RECORD_WORDS], p0[4], p1[4];
+                memcpy(rec, records + i, sizeof(rec));
+                wcpt_temporal_pack(rec, position, p0, p1);
+                wcpt_temporal_reproject(rec, p0, p1, *hist_cam, hist, (int)width, (int)height, k, &base[3 * i], &n_b[i]);
+            }
+    }
+    for (size_t i = 0; i < pixels; i++)
+        wcpt_temporal_blend(rgba + 4 * i, base + 3 * i, n_b[i], f, k, out_rgba + 4 * i, &out_length[i]);
+}
+
+/* ------------------------------------------------------------------------------------------------ */
 /* Denoise: the iterations of csrc/wcpt_denoise.h over float4 arrays and the packed guide            */
 
 struct HostImage {
@@ -1163,6 +1217,34 @@ int wcpt_denoise_host(const float* rgba, const wcpt_primary_hit* guide, uint32_t
     try {
         denoise_host(rgba, guide, width, height, p->iterations,
                      wcpt_denoise_make_consts(p->sigma_color, p->sigma_normal, p->sigma_depth), out_rgba32f, out_rgba8);
+    } catch (...) {
+        return WCPT_ERROR_OUT_OF_HOST_MEMORY;
+    }
+    return WCPT_SUCCESS;
+}
+
+int wcpt_temporal_host(const float* rgba, uint32_t frames, int restart, const wcpt_primary_hit* guide,
+                       const wcpt_scene_data* scene, uint32_t width, uint32_t height, const wcpt_temporal_params* t,
+                       const float* hist_rgba, const float* hist_length, const wcpt_primary_hit* hist_guide,
+                       const wcpt_scene_data* hist_scene, float* base, float* n_b, float* out_rgba, float* out_length)
+{
+    static_assert(sizeof(wcpt_primary_hit) == WCPT_TEMPORAL_RECORD_BYTES, "wcpt_primary_hit");
+    if (!rgba || !guide || !scene || !t || !base || !n_b || !out_rgba || !out_length || frames == 0 ||
+        !wcpt_temporal_params_ok(t->max_history, t->normal_min, t->depth_tol))
+        return WCPT_ERROR_INVALID_ARGUMENT;
+    if (width == 0 || height == 0 || width > 0x7FFFFFFFu || height > 0x7FFFFFFFu) return WCPT_ERROR_INVALID_ARGUMENT;
+    const bool history = restart && (hist_rgba || hist_length || hist_guide || hist_scene);
+    if (history && (!hist_rgba || !hist_length || !hist_guide || !hist_scene)) return WCPT_ERROR_INVALID_ARGUMENT;
+    wcpt_temporal_camera cam, hist_cam;
+    if (!wcpt_temporal_make_camera(scene->inverseProjection, scene->inverseView, scene->position, width, height, &cam))
+        return WCPT_ERROR_INVALID_ARGUMENT;
+    if (history && !wcpt_temporal_make_camera(hist_scene->inverseProjection, hist_scene->inverseView, hist_scene->position,
+                                              width, height, &hist_cam))
+        return WCPT_ERROR_INVALID_ARGUMENT;
+    try {
+        temporal_host(rgba, (float)frames, restart != 0, guide, cam.position, width, height,
+                      wcpt_temporal_make_consts(t->max_history, t->normal_min, t->depth_tol), history ? hist_rgba : nullptr,
+                      hist_length, hist_guide, &hist_cam, base, n_b, out_rgba, out_length);
     } catch (...) {
         return WCPT_ERROR_OUT_OF_HOST_MEMORY;
     }

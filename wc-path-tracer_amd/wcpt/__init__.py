@@ -3,7 +3,7 @@
 The compute lives in libwcpt.so (hand-written HIP for gfx950 behind the C-ABI of include/wcpt.h); this
 package is the Python host mirror used by tests and the benchmark.
 """
-from ._lib import (BloomParams, DenoiseParams, COUNTER_FIELDS, DRAW_COMMAND_DTYPE, EXPORTED_SYMBOLS, KERNEL_AUTO, KERNEL_MEGAKERNEL,
+from ._lib import (BloomParams, DenoiseParams, TemporalParams, COUNTER_FIELDS, DRAW_COMMAND_DTYPE, EXPORTED_SYMBOLS, KERNEL_AUTO, KERNEL_MEGAKERNEL,
                    KERNEL_WAVEFRONT, LIB_PATH, MATERIAL_DIELECTRIC, MATERIAL_DTYPE, MATERIAL_METAL, NODE_DTYPE,
                    SCENE_DATA_DTYPE, SPHERE_DTYPE, PRIMARY_HIT_DTYPE, HIT_MISS, HIT_SPHERE, HIT_TRIANGLE, HIT_KIND_MASK,
                    HIT_FRONT, Camera, WcptError, lib)
@@ -16,7 +16,7 @@ __all__ = [
     "KERNEL_WAVEFRONT", "LIB_PATH", "MATERIAL_DIELECTRIC", "MATERIAL_DTYPE", "MATERIAL_METAL", "NODE_DTYPE",
     "SCENE_DATA_DTYPE", "SPHERE_DTYPE", "Camera", "WcptError", "lib", "Context", "DeviceScene",
     "PathTracingRenderer", "Editor", "Group", "group_unique_id", "scene", "device_count", "device_pci_bus_id", "runtime_version", "build_id",
-    "BloomParams", "bloom_levels", "bloom_host", "DenoiseParams", "denoise_host",
+    "BloomParams", "bloom_levels", "bloom_host", "DenoiseParams", "denoise_host", "TemporalParams", "temporal_host",
     "PRIMARY_HIT_DTYPE", "HIT_MISS", "HIT_SPHERE", "HIT_TRIANGLE", "HIT_KIND_MASK", "HIT_FRONT",
 ]
 
@@ -93,3 +93,45 @@ def denoise_host(img, guide, params=None):
     _lib.check(lib.wcpt_denoise_host(_lib.ptr(a), _lib.ptr(g), a.shape[1], a.shape[0], C.byref(params), _lib.ptr(out32),
                                      _lib.ptr(out8)))
     return out32, out8
+
+
+def temporal_host(img, frames, guide, sd, params=None, restart=True, history=None, state=None):
+    """wcpt_temporal_host: one call of Context.composite(dst, temporal=params, ...)'s state sequence on the CPU by the same
+    arithmetic (no GPU needed), stateless. `img` is the accumulation image [H][W][4] of `frames` samples, `guide` its
+    primary-hit records [H][W] and `sd` its scene data. A restart takes `history`, None or (rgba, length, guide, sd) of the
+    previous sequence's last call -- that call's outputs with the records and scene data it was given at its restart; any
+    other call takes `state` = (base, n_b) as the sequence's restart returned them. Returns (base [H][W][3], n_b [H][W],
+    rgba [H][W][4], length [H][W]); rgba is what then goes through the display step or denoise_host."""
+    import ctypes as C
+    import numpy as np
+    a = np.ascontiguousarray(img, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("temporal_host: an image of shape (height, width, 4)")
+    h, w = a.shape[:2]
+    g = np.ascontiguousarray(guide, dtype=PRIMARY_HIT_DTYPE)
+    if g.shape != (h, w):
+        raise ValueError("temporal_host: one record per pixel, shape (height, width)")
+    s = np.ascontiguousarray(sd, dtype=SCENE_DATA_DTYPE)
+    params = TemporalParams() if params is None else params
+    hist = [None] * 4
+    if restart:
+        base, n_b = np.empty((h, w, 3), np.float32), np.empty((h, w), np.float32)
+        if history is not None:
+            hist = [np.ascontiguousarray(history[0], dtype=np.float32), np.ascontiguousarray(history[1], dtype=np.float32),
+                    np.ascontiguousarray(history[2], dtype=PRIMARY_HIT_DTYPE),
+                    np.ascontiguousarray(history[3], dtype=SCENE_DATA_DTYPE)]
+            if hist[0].shape != a.shape or hist[1].shape != (h, w) or hist[2].shape != (h, w):
+                raise ValueError("temporal_host: a history of the image's size")
+    else:
+        if state is None:
+            raise ValueError("temporal_host: a call that is no restart needs the sequence's (base, n_b)")
+        base = np.ascontiguousarray(state[0], dtype=np.float32)
+        n_b = np.ascontiguousarray(state[1], dtype=np.float32)
+        if base.shape != (h, w, 3) or n_b.shape != (h, w):
+            raise ValueError("temporal_host: base of shape (height, width, 3), n_b of shape (height, width)")
+    out = np.empty(a.shape, np.float32)
+    length = np.empty((h, w), np.float32)
+    _lib.check(lib.wcpt_temporal_host(_lib.ptr(a), frames, 1 if restart else 0, _lib.ptr(g), _lib.ptr(s), w, h,
+                                      C.byref(params), *[None if x is None else _lib.ptr(x) for x in hist], _lib.ptr(base),
+                                      _lib.ptr(n_b), _lib.ptr(out), _lib.ptr(length)))
+    return base, n_b, out, length

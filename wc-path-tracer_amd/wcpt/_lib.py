@@ -197,6 +197,14 @@ class DenoiseParams(C.Structure):
         super().__init__(iterations, sigma_color, sigma_normal, sigma_depth)
 
 
+class TemporalParams(C.Structure):
+    """wcpt_temporal_params (include/wcpt.h): the callers' defaults are max_history 32, normal_min 0.9, depth_tol 0.05."""
+    _fields_ = [("max_history", C.c_uint32), ("normal_min", C.c_float), ("depth_tol", C.c_float), ("_pad", C.c_uint32)]
+
+    def __init__(self, max_history: int = 32, normal_min: float = 0.9, depth_tol: float = 0.05):
+        super().__init__(max_history, normal_min, depth_tol, 0)
+
+
 class SceneC(C.Structure):
     _fields_ = [("mesh", Mesh), ("materials", C.c_void_p), ("material_count", C.c_uint32),
                 ("spheres", C.c_void_p), ("sphere_count", C.c_uint32), ("camera", Camera)]
@@ -241,6 +249,10 @@ _PROTOTYPES = {
     "wcpt_bloom_host": (_i, [_p, _u32, _u32, C.POINTER(BloomParams), _p, _p]),
     "wcpt_composite_denoise": (_i, [_p, _u64, _u64, _u64, _i, C.POINTER(DenoiseParams)]),
     "wcpt_denoise_host": (_i, [_p, _p, _u32, _u32, C.POINTER(DenoiseParams), _p, _p]),
+    "wcpt_composite_temporal": (_i, [_p, _p, _u32, _i, _u64, _u64, _u64, _i, C.POINTER(TemporalParams),
+                                     C.POINTER(DenoiseParams)]),
+    "wcpt_temporal_reset": (_i, [_p]),
+    "wcpt_temporal_host": (_i, [_p, _u32, _i, _p, _p, _u32, _u32, C.POINTER(TemporalParams), _p, _p, _p, _p, _p, _p, _p, _p]),
     "wcpt_render": (_i, [_p, _p, _u64, _u64, _u64]),
     "wcpt_sync": (_i, [_p]),
     "wcpt_primary_cache_stats": (_i, [_p, C.POINTER(_u64), C.POINTER(_u64)]),

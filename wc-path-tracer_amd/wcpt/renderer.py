@@ -171,13 +171,31 @@ class Context:
 
     # -- dispatch ---------------------------------------------------------------------------------------
     def composite(self, dst: int, rgba8: bool = False, bloom=None, denoise=None, guide: int | None = None,
-                  guide_bytes: int | None = None):
+                  guide_bytes: int | None = None, temporal=None, scene=None, frames: int | None = None,
+                  restart: bool = False):
         """composite.comp into device memory at `dst` (asynchronous); with `bloom` (a BloomParams) its Bloom branch is
         taken: bloom.comp's pyramid of the image is added before gamma and the tonemap (wcpt_composite_bloom). With
         `denoise` (a DenoiseParams) the image goes through the guided a-trous filter first (wcpt_composite_denoise):
         `guide` is the device address of the frame's primary-hit records (trace_primary) and `guide_bytes` the size of
-        the memory there (default width * height * 48). Denoise and bloom in one call are not provided."""
-        if denoise is not None:
+        the memory there (default width * height * 48). Denoise and bloom in one call are not provided.
+        With `temporal` (a TemporalParams) the image is first blended with the previous result reprojected to this
+        frame (wcpt_composite_temporal), then displayed or, with `denoise`, filtered: `scene` is the scene data of the
+        accumulated frames, `frames` the samples in the image (the last render's renderedFramesCount + 1), `restart`
+        whether the accumulation restarted since the previous such call, `guide` the records for this camera. Temporal
+        and bloom in one call are not provided."""
+        if temporal is not None:
+            if bloom is not None:
+                raise ValueError("composite: temporal and bloom in one call are not provided")
+            if guide is None or scene is None or frames is None:
+                raise ValueError("composite: temporal needs the guide (the records of trace_primary), the scene data and "
+                                 "the number of accumulated frames")
+            if guide_bytes is None:
+                guide_bytes = self.width * self.height * PRIMARY_HIT_DTYPE.itemsize
+            sd = np.ascontiguousarray(scene, dtype=SCENE_DATA_DTYPE)
+            self._chk(lib.wcpt_composite_temporal(self.h, ptr(sd), frames, 1 if restart else 0, guide, guide_bytes, dst,
+                                                  1 if rgba8 else 0, C.byref(temporal),
+                                                  None if denoise is None else C.byref(denoise)))
+        elif denoise is not None:
             if bloom is not None:
                 raise ValueError("composite: denoise and bloom in one call are not provided")
             if guide is None:
@@ -189,6 +207,11 @@ class Context:
             self._chk(lib.wcpt_composite(self.h, dst, 1 if rgba8 else 0))
         else:
             self._chk(lib.wcpt_composite_bloom(self.h, dst, 1 if rgba8 else 0, C.byref(bloom)))
+
+    def temporal_reset(self):
+        """wcpt_temporal_reset: the next composite(temporal=...) starts without history (a material, light or mesh
+        change, which the records cannot see)."""
+        self._chk(lib.wcpt_temporal_reset(self.h))
 
     def render(self, sd: np.ndarray, materials: int, spheres: int, draws: int):
         sd = np.ascontiguousarray(sd, dtype=SCENE_DATA_DTYPE)
@@ -458,6 +481,8 @@ class PathTracingRenderer:
         self._guide_buf = None           # Composite(denoise=...): the primary-hit records of the accumulated frames
         self._guide_bytes = 0
         self._guide_stale = True
+        self._temporal_restart = True    # Composite(temporal=...): the guide was retraced since the last temporal call
+        self._mat_uploaded = None        # the materials of the last UpdateMaterials, as bytes
 
     # Init :272-343 — LoadModel + materials/spheres + UpdateMaterials
     def Init(self, model_path: str | None = None, scene: "_scene.HostScene | None" = None, build: str = "host",
@@ -527,6 +552,7 @@ class PathTracingRenderer:
             self.ctx.buffer_upload(nb, new.nodes)
         self.renderedFramesCount = 0
         self._guide_stale = True
+        self.ctx.temporal_reset()
 
     # PushMaterial :492-496
     def PushMaterial(self) -> int:
@@ -543,6 +569,13 @@ class PathTracingRenderer:
             self._sph_buf = self.ctx.buffer_alloc(0)
         self.ctx.buffer_upload(self._mat_buf, self.materials)
         self.ctx.buffer_upload(self._sph_buf, self.spheres)
+        # Composite(temporal=...): changed materials are nothing the records show, so they drop the history. The editor
+        # uploads every frame (editor.jai:154-158); an upload of the same materials keeps it, and so do moved spheres:
+        # the depth test rejects what moved
+        uploaded = self.materials.tobytes()
+        if self._mat_uploaded is not None and uploaded != self._mat_uploaded:
+            self.ctx.temporal_reset()
+        self._mat_uploaded = uploaded
 
     # CreateScreen :345-385
     def CreateScreen(self, size):
@@ -582,12 +615,14 @@ class PathTracingRenderer:
     def Readback(self) -> np.ndarray:
         return self.ctx.readback()
 
-    def Composite(self, camera: Camera, dst: int, rgba8: bool = False, denoise=None):
-        """The display step into device memory at `dst` (Context.composite). With `denoise` (a DenoiseParams) the
-        renderer keeps a guide buffer of its own and traces it with Context.trace_primary only when it is stale: on first
-        use, after Resize, after UpdateMesh, and after any Render whose renderedFramesCount was 0 -- the editor's
-        protocol: whatever moves, the count restarts."""
-        if denoise is None:
+    def Composite(self, camera: Camera, dst: int, rgba8: bool = False, denoise=None, temporal=None):
+        """The display step into device memory at `dst` (Context.composite). With `denoise` (a DenoiseParams) or
+        `temporal` (a TemporalParams) the renderer keeps a guide buffer of its own and traces it with
+        Context.trace_primary only when it is stale: on first use, after Resize, after UpdateMesh, and after any Render
+        whose renderedFramesCount was 0 -- the editor's protocol: whatever moves, the count restarts. That moment is also
+        the temporal stage's restart; Resize, UpdateMesh and an UpdateMaterials with changed materials drop its history (a
+        moved sphere does not: the depth test rejects what moved)."""
+        if denoise is None and temporal is None:
             self.ctx.composite(dst, rgba8=rgba8)
             return
         w, h = self.renderSize
@@ -599,11 +634,18 @@ class PathTracingRenderer:
             self._guide_bytes = nbytes
             self._guide_stale = True
         guide = self.ctx.buffer_address(self._guide_buf)
+        sd = self.scene_data(camera)
         if self._guide_stale:
-            self.ctx.trace_primary(self.scene_data(camera), self.ctx.buffer_address(self._sph_buf),
-                                   self.ctx.buffer_address(self._draw_buf), guide, self._guide_bytes)
+            self.ctx.trace_primary(sd, self.ctx.buffer_address(self._sph_buf), self.ctx.buffer_address(self._draw_buf), guide,
+                                   self._guide_bytes)
             self._guide_stale = False
-        self.ctx.composite(dst, rgba8=rgba8, denoise=denoise, guide=guide, guide_bytes=self._guide_bytes)
+            self._temporal_restart = True
+        if temporal is None:
+            self.ctx.composite(dst, rgba8=rgba8, denoise=denoise, guide=guide, guide_bytes=self._guide_bytes)
+            return
+        self.ctx.composite(dst, rgba8=rgba8, denoise=denoise, guide=guide, guide_bytes=self._guide_bytes, temporal=temporal,
+                           scene=sd, frames=max(1, self.renderedFramesCount), restart=self._temporal_restart)
+        self._temporal_restart = False
 
     def Pick(self, camera: Camera, x: int, y: int):
         """What pixel (x, y) of the frame shows from `camera` (wcpt_pick): (record, position) -- the PRIMARY_HIT_DTYPE
