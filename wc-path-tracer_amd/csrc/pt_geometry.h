@@ -117,11 +117,10 @@ struct ChildPair {
     __device__ __forceinline__ float nearT0() const { return leftFirst ? l0 : r0; }
     __device__ __forceinline__ float farT0() const { return leftFirst ? r0 : l0; }
 };
-__device__ __forceinline__ ChildPair child_pair(const Ray& ray, const NodeV& L, const NodeV& R)
+/* The decision on the two boxes' slab distances (l0, l1) and (r0, r1): the tiny walk passes a box's distances on from
+ * a node whose bound words are the same bits (pt_tiny.h tiny_walk) instead of evaluating node_box on them again. */
+__device__ __forceinline__ ChildPair child_pair(float l0, float l1, float r0, float r1)
 {
-    float l0, l1, r0, r1;
-    node_box(ray, L, l0, l1);
-    node_box(ray, R, r0, r1);
     const float leftDist = (l0 > 0.0f) ? l0 : l1;
     const float rightDist = (r0 > 0.0f) ? r0 : r1;
     ChildPair c;
@@ -133,12 +132,34 @@ __device__ __forceinline__ ChildPair child_pair(const Ray& ray, const NodeV& L, 
     c.r0 = r0;
     return c;
 }
-/* The root's cull (:152-162): pushed untested, popped and tested against rec.t; whether it survives. */
+__device__ __forceinline__ ChildPair child_pair(const Ray& ray, const NodeV& L, const NodeV& R)
+{
+    float l0, l1, r0, r1;
+    node_box(ray, L, l0, l1);
+    node_box(ray, R, r0, r1);
+    return child_pair(l0, l1, r0, r1);
+}
+/* The root's cull (:152-162): pushed untested, popped and tested against rec.t; whether it survives. On the root box's
+ * slab distances (c0, c1), and on the node. */
+__device__ __forceinline__ bool root_survives(float c0, float c1, float rt)
+{
+    return !(c0 > c1 || c1 < 0.0f || c0 > rt);
+}
 __device__ __forceinline__ bool root_survives(const Ray& ray, const NodeV& root, float rt)
 {
     float c0, c1;
     node_box(ray, root, c0, c1);
-    return !(c0 > c1 || c1 < 0.0f || c0 > rt);
+    return root_survives(c0, c1, rt);
+}
+/* Whether two nodes' six bound words are the same bits, for nodes held in SGPRs (load_node_const): an integer compare on
+ * the scalar unit, wave-uniform. Bitwise, so -0 against +0 and a NaN against anything are "different" and the caller
+ * evaluates the box itself. */
+__device__ __forceinline__ bool same_box_bits(const NodeV& a, const NodeV& b)
+{
+    auto u = [](float f) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(f)); };
+    auto w = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+    return ((u(a.a.x) ^ u(b.a.x)) | (u(a.a.y) ^ u(b.a.y)) | (u(a.a.z) ^ u(b.a.z)) | (u(a.a.w) ^ u(b.a.w)) |
+            (w(a.b.x) ^ w(b.b.x)) | (w(a.b.y) ^ w(b.b.y))) == 0u;
 }
 
 /* pathTracer.comp:110-119, near root only (:141) */

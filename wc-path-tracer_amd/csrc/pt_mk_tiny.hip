@@ -24,15 +24,18 @@
 namespace wcpt {
 namespace dev {
 
-/* Occupancy floors (__launch_bounds__'s minimum waves per SIMD), chosen by measurement (profiles/tiny_kernels_ab.log
- * section 3): the compiler's own allocation is 81-85 VGPRs for the heads (5 waves) and 77 for the tail (6 waves). A floor
- * of 6 brings the heads to 78-79 VGPRs at 16-32 bytes of scratch and c2 from 0.2410 to 0.2367 ms; 7 (72 VGPRs, 32-48
- * bytes of scratch in all four) measured 0.2374 and 8 no better; the tail at 7 with the heads at 6 measured 0.2404. */
+/* Occupancy floors (__launch_bounds__'s minimum waves per SIMD), chosen by measurement (profiles/tiny_regs_ab.log sections
+ * 3 and 4; the earlier sweep is profiles/tiny_kernels_ab.log section 3). With the accumulation read behind the trace (below)
+ * the compiler's own allocation is 79-83 VGPRs for the heads and 73 for the tail. A floor of 7 on all four -- 72 VGPRs; 32-48
+ * bytes of scratch in the heads, none in the tail, which pays its one register with SGPRs spilled to VGPR lanes -- measured c2
+ * 0.2335 ms against 0.2363 at the earlier floor of 6 with the early read. The floors only pay together: heads 7 with the tail
+ * at 6 measured 0.2381, heads 6 with the tail at 7 0.2389, 6 / 6 0.2359, heads 8 0.2376. The two pipes' heads and tails share
+ * the SIMDs, and seven waves fit in any mix only when every kernel is at 72. */
 #ifndef WCPT_TINY_HEAD_WAVES
-#define WCPT_TINY_HEAD_WAVES 6
+#define WCPT_TINY_HEAD_WAVES 7
 #endif
 #ifndef WCPT_TINY_TAIL_WAVES
-#define WCPT_TINY_TAIL_WAVES 6
+#define WCPT_TINY_TAIL_WAVES 7
 #endif
 /* For experiments (tools/ab_build.sh): dynamic LDS bytes per wave that the kernels never touch, which caps the waves
  * a CU holds at 160 KiB / this, with the same instruction stream. */
@@ -60,10 +63,7 @@ __device__ __forceinline__ void tiny_head_pixel(const wcpt_scene_data& sd, const
     if constexpr (PC != kPrimCacheRead) dir = primary_direction(sd, x, y, W, H);
     const uint32_t pixel_index = x + y * W + sd.renderedFramesCount * 719393u; /* :304 */
     uint32_t rng = pcg_hash(pixel_index);
-    /* the accumulation read (:314) ahead of the trace, and the cache entry beside it: as in shade_pixel */
     const uint32_t pixel = (uint32_t)((size_t)ly * W + lx);
-    float4 old = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (sd.renderedFramesCount != 0) old = image[(size_t)ly * W + lx];
     const f3 origin = mk3(sd.position[0], sd.position[1], sd.position[2]);
     PathState ps;
     f3 L = mk3(0.0f, 0.0f, 0.0f);
@@ -104,6 +104,11 @@ __device__ __forceinline__ void tiny_head_pixel(const wcpt_scene_data& sd, const
             if (done) break;
         }
     }
+    /* The accumulation read (:314) behind the trace, unlike shade_pixel's, which reads ahead of it: there the four words are
+     * live across every segment, registers that the floor of 7 would have to spill. The pixel is this lane's alone, in the
+     * head or in the tail, so the value is the same; the other waves of the SIMD cover the read's latency, once per pixel. */
+    float4 old = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (sd.renderedFramesCount != 0) old = image[(size_t)ly * W + lx];
     /* shade_pixel's `result + TraceRay(...)` from a zero sum: the same addition, so a -0 radiance becomes +0 here too */
     accumulate_store(sd, image, wire, wire_ch, wm, W, lx, ly, old, mk3(0.0f, 0.0f, 0.0f) + L);
 }
@@ -155,16 +160,17 @@ __global__ __launch_bounds__(64, WCPT_TINY_TAIL_WAVES) void pt_tiny_tail(
     PathState ps;
     uint32_t rng, pixel;
     split_load<A>(q, i, ps, rng, pixel);
-    const uint32_t lx = pixel % W, ly = pixel / W;
-    /* the accumulation read first, as in the head */
-    float4 old = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (sd.renderedFramesCount != 0) old = image[pixel];
     /* TraceTail: from segment `cut` on, never a primary segment, the pixel's one and last sample */
     f3 L;
     for (;;) {
         const Hit h = tiny_intersect<A>(ps.ray, sd, spheres, draws, tri_records, false);
         if (path_shade<kShadeA<A>>(ps, h, rng, sd, mats, L, true)) break;
     }
+    /* the pixel's coordinates and its accumulation read behind the trace, as in the head: six registers that the
+     * segments do not hold (77 -> 73 VGPRs of its own; the floor takes the last one) */
+    const uint32_t lx = pixel % W, ly = pixel / W;
+    float4 old = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (sd.renderedFramesCount != 0) old = image[pixel];
     accumulate_store(sd, image, wire, wire_ch, wm, W, lx, ly, old, mk3(0.0f, 0.0f, 0.0f) + L);
 }
 

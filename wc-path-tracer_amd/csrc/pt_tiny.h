@@ -2,7 +2,7 @@
  * kernels of pt_mk_tiny.hip run it: no traversal loop, no stack, no mode. Exact arithmetic on pair records, one draw.
  *
  * The nodes are the same for every lane, so the wave reads them with scalar loads and the leaves' record ranges are SALU
- * values. What stays per lane is the reference's own arithmetic and its decisions -- the three slab tests, root_step's
+ * values. What stays per lane is the reference's own arithmetic and its decisions -- the slab tests (one per distinct box: tiny_walk), root_step's
  * cull (root_survives), interior_step's order and its two box passes (child_pair), the pop's cull of the far child
  * against the rec.t the near leaf left -- through the same definitions as the traversal loop, NaN behaviour included. A
  * leaf is run by the whole wave under a wave-uniform branch (some lane visits it), and a lane that the reference would
@@ -144,7 +144,9 @@ __device__ __forceinline__ void tiny_walk(const Ray& ray, const DrawGeom& g, boo
 {
     const NodeV root = load_node_const(g.bvh, 0);
     TinyLane t;
-    t.in = root_survives(ray, root, rt);
+    float c0, c1;
+    node_box(ray, root, c0, c1);
+    t.in = root_survives(c0, c1, rt);
     t.c = ChildPair{false, false, false, 0.0f, 0.0f};
     uint32_t firstL = root.b.z, countL = root.b.w, firstR = 0u, countR = 0u; /* a root leaf: the "left" one */
     TinyRanges r;
@@ -152,7 +154,27 @@ __device__ __forceinline__ void tiny_walk(const Ray& ray, const DrawGeom& g, boo
     if (r.two) { /* wave-uniform: interior_step on the two leaves */
         const NodeV L = load_node_const(g.bvh, root.b.z);
         const NodeV R = load_node_const(g.bvh, root.b.z + 1u);
-        t.c = child_pair(ray, L, R);
+        /* A box whose six bound words are the bits of one already tested has that one's slab distances: node_box is a
+         * function of the ray and those words alone. Midpoint leaves over a room's walls both span the whole room, which
+         * is the root's box, so the Cornell walk makes one slab test per segment instead of three. The nodes are in
+         * SGPRs; the compares are scalar and the branches wave-uniform. */
+        float l0, l1, r0, r1;
+        if (same_box_bits(L, root)) {
+            l0 = c0;
+            l1 = c1;
+        } else {
+            node_box(ray, L, l0, l1);
+        }
+        if (same_box_bits(R, root)) {
+            r0 = c0;
+            r1 = c1;
+        } else if (same_box_bits(R, L)) {
+            r0 = l0;
+            r1 = l1;
+        } else {
+            node_box(ray, R, r0, r1);
+        }
+        t.c = child_pair(l0, l1, r0, r1);
         firstL = L.b.z;
         countL = L.b.w;
         firstR = R.b.z;
